@@ -7,11 +7,17 @@ timed region = MPCFlat::CalcPosteriors + MPCFlat::Consistency, mpcflat.cpp:313,3
 (sequences, HMM tables) are resident on the device before the timed region. Synthetic protein
 family (muscle_amd/synth.py, seed 1), default N=1000 L~400 = BASELINE configs[2].
 
-  python bench.py [--gpus N --steps K --warmup W] [--n 1000 --len 400]
+  python bench.py [--gpus N --steps K --warmup W] [--n 1000 --len 400] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
        (pairs sharded over ranks, RCCL all-gather of sparse posteriors before relax; weak=no:
         total work is fixed, so "scaling": "strong")
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (roofline figures included: they come from the
+timed steps' own device timers and committed counter passes). --full adds what takes work of its own after the timed
+region: the digest self-check against the compiled reference's output, the real-data leg and the CPU baseline
+(--no-parity / --no-real-data / --no-cpu-baseline leave out one of them). --dump-outputs DIR writes what the last timed
+step computed (dump_outputs below) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -79,6 +85,55 @@ def parity_check(g, a):
     err = D.compare_ea(z, g.get_ea()) or D.compare_stage(z, 2, g)
     return ("match", "EA bits and stage-2 sparse posteriors (offsets, columns, float bits) of all pairs equal the "
             "reference's: tests/golden/mpcbig_%s.npz" % name) if err is None else ("MISMATCH", err)
+
+
+DUMP_BYTES = 64 * 10**6     # --dump-outputs: at most this much in all
+DUMP_EA_PAIRS = 1 << 20     # per-pair figures of every pair up to this many pairs, else of a seeded sample of this many
+DUMP_STORE_PAIRS = 1024     # sparse posterior matrices of a seeded sample of this many pairs
+
+
+def dump_outputs(g, d):
+    """--dump-outputs: what a caller of the timed path (MPCFlat::CalcPosteriors + Consistency) receives after the last timed step,
+    as .npy files in d; pairs are numbered in InitPairs order, integers are stored as float64 (exact):
+      ea.npy (f32), nnz.npy (f64)    per pair: the expected-accuracy score and the number of stored posteriors — of every pair, or
+                                     of the pairs listed in pairs.npy (seeded sample, sorted) when there are more than DUMP_EA_PAIRS
+      store_pairs.npy (f64)          a seeded sample of pairs (sorted) whose sparse posterior matrices follow, back to back:
+      store_offsets.npy (f64)        LX + 1 row offsets per pair
+      store_post.npy (f32), store_col.npy (f64)   posterior and column of every stored cell
+    The matrix sample ends early where the files would pass DUMP_BYTES in all. The same arguments give the same inputs, so two
+    builds can be compared file by file."""
+    os.makedirs(d, exist_ok=True)
+    npairs = g.npairs
+    ea, nnz = g.get_ea(), g.get_nnz()
+    files = {}
+    if npairs > DUMP_EA_PAIRS:
+        pick = np.sort(np.random.default_rng(1).choice(npairs, DUMP_EA_PAIRS, replace=False))
+        files["pairs"] = pick.astype(np.float64)
+        ea, nnz = ea[pick], nnz[pick]
+    files["ea"] = ea.astype(np.float32)
+    files["nnz"] = nnz.astype(np.float64)
+    used = sum(v.nbytes for v in files.values()) + 128 * (len(files) + 4)  # + the .npy headers
+    ks, offs, post, col = [], [], [], []
+    for k in np.sort(np.random.default_rng(2).choice(npairs, min(npairs, DUMP_STORE_PAIRS), replace=False)):
+        (o, v), = g.get_sparse_range(int(k), int(k) + 1)
+        size = 8 + 8 * len(o) + 6 * len(v)  # pair number + offsets + 12 bytes per cell (v holds two words per cell)
+        if used + size > DUMP_BYTES:
+            break
+        used += size
+        ks.append(k)
+        offs.append(o)
+        post.append(v[0::2].view(np.float32))
+        col.append(v[1::2])
+
+    def cat(parts, dtype):
+        return np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype)
+
+    files["store_pairs"] = np.asarray(ks, np.float64)
+    files["store_offsets"] = cat(offs, np.float64)
+    files["store_post"] = cat(post, np.float32)
+    files["store_col"] = cat(col, np.float64)
+    for name, arr in files.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def real_data_leg(g, torch, run_stage, steps=1):
@@ -245,10 +300,18 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--fasta", default=None, help="real sequences instead of the synthetic family: first --n records of this FASTA "
                     "(.gz accepted), e.g. tests/golden/rdrp_first1000.fa.gz (first 1000 records of the reference's test_data/rdrp/rdrp.fa)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the digest self-check after the timed region")
-    ap.add_argument("--no-real-data", action="store_true", help="skip the real-data leg (rdrp, first 1000 records) after the synthetic timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the digest self-check, the real-data leg "
+                    "and the CPU baseline (a plain run measures the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the digest self-check after the timed region")
+    ap.add_argument("--no-real-data", action="store_true", help="with --full: skip the real-data leg (rdrp, first 1000 records) after the synthetic timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(one GPU only)")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if a.dump_outputs and a.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (a rank of a sharded run holds part of the store)")
 
     from muscle_amd.hostinfo import pin_openmp_team
     pin_openmp_team()
@@ -319,6 +382,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     timers = g.timers_get()
+    if a.dump_outputs:
+        dump_outputs(g, a.dump_outputs)
     rc = 0
     # every rank's phases (host seconds between the points where run_stage waits for the device anyway), and how many ranks the
     # collective backend really connected: rank 0 prints the maximum over ranks and the list
@@ -516,15 +581,15 @@ def main():
                         "commit under it; commit: the other ranks' slices)"}
         if dry:
             out["dry_run"] = True
-        elif not a.no_parity:
+        elif a.full and not a.no_parity:
             out["parity_digest"], out["parity_detail"] = parity_check(g, a)
         # the realistic input, after the synthetic timed region and its self-check (one GPU, the default workload only)
-        if world == 1 and not dry and not a.fasta and not a.no_real_data and a.n == 1000 and a.len == 400:
+        if a.full and world == 1 and not dry and not a.fasta and not a.no_real_data and a.n == 1000 and a.len == 400:
             try:
                 out["real_data"] = real_data_leg(g, torch, run_stage)
             except Exception as e:  # noqa: BLE001 - the headline line must still be printed
                 out["real_data"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_cpu_baseline and not dry:
+        if a.full and world == 1 and not a.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(seqs, a.n)
         print(json.dumps(out), flush=True)
         if out.get("parity_digest") == "MISMATCH" or (out.get("real_data") or {}).get("parity_sample") == "MISMATCH":

@@ -2,8 +2,9 @@
 # Builds hostcxx/_build/muscle_gpu: the reference's own `muscle` with the MI355X posterior stage
 # linked in as a drop-in. Needs the reference objects that oracle/build_ref.sh
 # compiles from the sources where they lie ($MUSCLE_REF_SRC, default /root/reference/src) — nothing
-# of the reference is copied into the repo, and the combined (GPL-3.0) binary is git-ignored; it
-# travels to the GPU box as a built artefact.
+# of the reference is copied into the repo, and the combined (GPL-3.0) binary is git-ignored. A copy
+# is kept beside the compiled reference as oracle/_ref/muscle_gpu, which travels with it to a GPU
+# box: where the reference sources are absent, this script installs that copy instead of linking.
 #
 #   reference objects  - consflat.o, alnalnsflat.o, alnmsasflat.o, buildpostflat.o, alignpairflat.o, refineflat.o  (MPCFlat::ConsIter,
 #                        MPCFlat::AlignAlns, PProg::AlignMSAsFlat, MPCFlat::BuildPost, AlignPairFlat(_SparsePost) and
@@ -20,8 +21,15 @@ ROOT="$(dirname "$HERE")"
 SRC="${MUSCLE_REF_SRC:-/root/reference/src}"
 REFOBJ="$ROOT/oracle/_ref/obj"
 OUT="$HERE/_build"
+PREBUILT="$ROOT/oracle/_ref/muscle_gpu"
 if [ ! -d "$SRC" ] || [ ! -d "$REFOBJ" ]; then
-  echo "build_muscle_gpu.sh: reference sources/objects not available (run oracle/build_ref.sh where /root/reference exists) - skipping" >&2
+  if [ -z "${MPCGPU_BIN:-}" ] && [ -x "$PREBUILT" ]; then
+    mkdir -p "$OUT"
+    cp -p "$PREBUILT" "$OUT/muscle_gpu"
+    echo "installed: $OUT/muscle_gpu (from $PREBUILT; the reference sources are not here)"
+    exit 0
+  fi
+  echo "build_muscle_gpu.sh: reference sources/objects not available (run oracle/build_ref.sh where the reference sources are) - skipping" >&2
   exit 0
 fi
 mkdir -p "$OUT"
@@ -53,5 +61,9 @@ BIN="${MPCGPU_BIN:-muscle_gpu}"
 # --wrap=rand: the reference's rand() (refineflat.cpp:14) gets a private copy of glibc's default
 # stream; the HIP runtime in the same process otherwise consumes it (hostcxx/rand_isolate.cpp)
 g++ -O3 -fopenmp -pthread -Wl,--wrap=rand $OBJS "$OUT/calcposteriorflat_weak.o" "$OUT/super7_weak.o" "$OUT/uclust_weak.o" "$OUT/pprog2_weak.o" "$OUT/mpcflat_weak.o" "$OUT/progalnflat_weak.o" "$OUT/mpcflat_gpu.o" "$OUT/rand_isolate.o" \
-  -L"$LIBDIR" -l"$LIBNAME" -Wl,-rpath,"$LIBDIR" -Wl,-rpath,'$ORIGIN/../../muscle_amd/csrc' -Wl,-rpath,/opt/rocm/lib -o "$OUT/$BIN"
+  -L"$LIBDIR" -l"$LIBNAME" -Wl,-rpath,'$ORIGIN/../../muscle_amd/csrc' -Wl,-rpath,"$LIBDIR" -Wl,-rpath,/opt/rocm/lib -o "$OUT/$BIN"
 echo "built: $OUT/$BIN"
+# the product binary, beside the compiled reference (same depth below the root: the $ORIGIN run path holds from there too)
+if [ -z "${MPCGPU_BIN:-}" ]; then
+  cp -p "$OUT/$BIN" "$PREBUILT"
+fi

@@ -5,9 +5,9 @@
 #   env:K=V / unset:K     set / clear a library knob (scripts/README.md) for the steps that follow
 #   tests[:<-k expr>]     pytest -m gpu (-x), optionally restricted
 #   smoke                 __graft_entry__.smoke()
-#   bench[:N:L[:steps]]   bench.py --no-cpu-baseline on the synthetic family -> gpurun_out/<tag>_bench_<N>x<L>[_<label>].json
-#   benchcpu              the driver's default command (CPU baseline + parity self-check) -> gpurun_out/<tag>_bench_default.json
-#   rdrp[:n]              bench.py --fasta tests/golden/rdrp_first1000.fa.gz --n n (default 1000), one step
+#   bench[:N:L[:steps]]   bench.py --full --no-cpu-baseline on the synthetic family -> <tag>_bench_<N>x<L>[_<label>].json
+#   benchcpu              bench.py --full (CPU baseline + parity self-check + real-data leg) -> <tag>_bench_default.json
+#   rdrp[:n]              bench.py --full --fasta tests/golden/rdrp_first1000.fa.gz --n n (default 1000), one step
 #   stats[:N:L]           rocprofv3 --kernel-trace --stats of one bench step -> gpurun_out/<tag>_kernel_stats_<N>x<L>.csv
 #   pmc[:N:L]             separate --pmc passes (FETCH_SIZE, WRITE_SIZE, two SQ sets) of one bench step + scripts/pmc_summary.py
 #   rdrpstats / rdrppmc[:n] the same two on the rdrp input
@@ -35,12 +35,12 @@ for s in "$@"; do
 	tests) if [ -n "${a1:-}" ]; then TAILN=15 step timeout 1500 python -u -m pytest tests -m gpu -q -x -k "${s#tests:}"; else TAILN=15 step timeout 1500 python -u -m pytest tests -m gpu -q -x; fi;;
 	smoke) step timeout 120 python -u -c "import __graft_entry__ as g; g.smoke()";;
 	bench) N=${a1:-1000}; L=${a2:-400}; K=${a3:-2}
-		step timeout 900 python -u bench.py --n $N --len $L --steps $K --warmup 1 --no-cpu-baseline --no-real-data
+		step timeout 900 python -u bench.py --n $N --len $L --steps $K --warmup 1 --full --no-cpu-baseline --no-real-data
 		grep '^{"metric"' $LOG | tail -1 > $OUT/${TAG}_bench_${N}x${L}${LABEL}.json;;
-	benchcpu) step timeout 900 python -u bench.py
+	benchcpu) step timeout 900 python -u bench.py --full
 		grep '^{"metric"' $LOG | tail -1 > $OUT/${TAG}_bench_default${LABEL}.json;;
 	rdrp) N=${a1:-1000}
-		step timeout 900 python -u bench.py --fasta $RDRP --n $N --steps 1 --warmup 1 --no-cpu-baseline
+		step timeout 900 python -u bench.py --fasta $RDRP --n $N --steps 1 --warmup 1 --full --no-cpu-baseline
 		grep '^{"metric"' $LOG | tail -1 > $OUT/${TAG}_bench_rdrp${N}${LABEL}.json;;
 	stats) N=${a1:-1000}; L=${a2:-400}
 		prof ${TAG}_prof_stats --kernel-trace --stats -- --n $N --len $L

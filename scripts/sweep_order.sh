@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 VALS=${@:-pairs 1 2 4 8 16}
 for g in $VALS; do
   echo "== ORDER=$g"
-  MPCGPU_RELAX_ORDER=$g python -u $R/bench.py --n 1000 --len 400 --steps 2 --warmup 1 --no-cpu-baseline --no-real-data 2>/dev/null | python $R/scripts/benchline.py | head -1
+  MPCGPU_RELAX_ORDER=$g python -u $R/bench.py --n 1000 --len 400 --steps 2 --warmup 1 --full --no-cpu-baseline --no-real-data 2>/dev/null | python $R/scripts/benchline.py | head -1
 done
 cd /tmp
 for g in pairs 8; do

@@ -21,7 +21,8 @@ SETS = ["n2_L40", "n3_L30", "n8_L60", "ragged", "bb11001", "bb11005", "n32_L150"
 @pytest.fixture(scope="module")
 def gpu_muscle():
     if not os.path.exists(_msa.GPU_MUSCLE):
-        pytest.fail("hostcxx/_build/muscle_gpu missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail("hostcxx/_build/muscle_gpu missing: run __graft_entry__.build() where the reference sources are, "
+                    "or where oracle/_ref/muscle_gpu built there travelled along")
     return _msa.GPU_MUSCLE
 
 

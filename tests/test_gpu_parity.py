@@ -754,7 +754,7 @@ def test_two_gpus_rccl_group_and_torchrun_bench():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "2", "--nseqs", "256", "--seqlen", "300", "--steps", "1",
+                          "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "2", "--nseqs", "256", "--seqlen", "300", "--full", "--steps", "1",
                           "--warmup", "1"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert out.returncode == 0 and lines, out.stdout[-2000:] + out.stderr[-2000:]

@@ -344,3 +344,42 @@ def test_bench_py_world2_dry_run():
     assert mg["rccl_ranks"] == 2 and mg["backend"] == "gloo" and len(mg["phase_ms_per_rank"]) == 2 and sum(mg["pairs_per_rank"]) == 36
     assert {"stage_a", "exchange_shards", "import_store", "relax", "exchange_values", "commit"} <= set(mg["phase_ms_max_over_ranks"])
     assert "blocks of the pair triangle" in mg["partition"] and max(mg["sequences_held_per_rank"]) <= 9
+
+
+def test_bench_py_dump_outputs_dry_run(tmp_path):
+    """bench.py --dump-outputs on one "GPU" in the dry-run mode (the SIMT-emulator library on the CPU): the files hold what the
+    last timed step left for a caller — EA and stored cells of every pair and the matrices of the sampled pairs equal the
+    oracle's after two relax iterations, bit for bit — and a plain run carries no --full record."""
+    import json
+    import subprocess
+    import sys
+    import _parity as P
+    from muscle_amd.synth import make_family
+    _make_emu()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MPCGPU_BENCH_DRYRUN=EMU_LIB, OMP_NUM_THREADS="1")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--nseqs", "9", "--seqlen", "30", "--dump-outputs", str(tmp_path)],
+                       env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["config"]["pairs"] == 36
+    assert not {"parity_digest", "real_data", "cpu_baseline"} & set(d)
+    f = {n[:-4]: np.load(os.path.join(tmp_path, n)) for n in os.listdir(tmp_path)}
+    assert set(f) == {"ea", "nnz", "store_pairs", "store_offsets", "store_post", "store_col"}
+    assert all(a.dtype in (np.float32, np.float64) for a in f.values())
+    stages, ea = P.run_oracle(make_family(9, 30, seed=1))
+    last = stages[-1]
+    assert np.array_equal(P.bits(f["ea"]), P.bits(ea))
+    assert np.array_equal(f["nnz"], [len(v) // 2 for _, v in last])
+    assert np.array_equal(f["store_pairs"], np.arange(36))  # 36 pairs: all of them are sampled
+    po = pv = 0
+    for k in range(36):
+        o, v = last[k]
+        assert np.array_equal(f["store_offsets"][po:po + len(o)], o), k
+        assert np.array_equal(P.bits(f["store_post"][pv:pv + len(v) // 2]), v[0::2]), k
+        assert np.array_equal(f["store_col"][pv:pv + len(v) // 2], v[1::2]), k
+        po, pv = po + len(o), pv + len(v) // 2
+    assert po == len(f["store_offsets"]) and pv == len(f["store_post"]) == len(f["store_col"])
