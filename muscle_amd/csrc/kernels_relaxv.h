@@ -36,8 +36,6 @@ struct RelaxVarParams {
 	const u32 *tiles; // 4 u32 per tile: x0, nx, y0, ny
 	u32 ntiles;
 	u64 k0, k1;    // only pairs in [k0,k1) are relaxed (multi-GPU shard)
-	u32 nbuf;      // LDS staging buffers: 2 = DMA of step Z+1 under the merges of step Z, 1 = DMA, wait, merge
-	u32 buf_bytes; // capacity of one staging buffer (the second starts buf_bytes after the first)
 	u32 *tile_next; // 8 counters, zeroed before the launch: next tile of each XCD's range
 };
 
@@ -57,7 +55,7 @@ struct RelaxVarParams {
 	} while (0)
 
 // The merge of one (cell, Z) in C++: the statement of what MpcRvBlocksAsm (mpc_platform.h) does with hand-scheduled
-// instructions. The emulator runs this one; on the device it is the MPCGPU_RELAX_MERGE=cxx instantiation (A/B).
+// instructions. The emulator runs this one; on the device relax_band_kernel's MPCGPU_RELAX_MERGE=cxx instantiations do (A/B).
 __device__ __forceinline__ void mpc_rv_merge_cxx(float &sum, MpcQuad va, MpcQuad vb, u32 ia, u32 ib)
 {
 	MPC_RV_TERMS(sum, va, vb);
@@ -98,7 +96,9 @@ typedef MpcRvBlocksCxx MpcRvBlocksAsm; // the emulator has the C++ statement onl
 // DIAG (measurement only, results wrong): 1 = staging and barriers only, 2 = merges only (step 0's records for every step,
 // no further staging, no barriers), 3 = as 2 with the two barriers per step.
 // WGS: workgroups per CU the register allocation has to allow (waves per SIMD = WGS * THREADS / 256).
-// BLOCKS: MpcRvBlocksAsm (hand-scheduled merge, the default) or MpcRvBlocksCxx.
+// BLOCKS: MpcRvBlocksAsm (hand-scheduled merge) or MpcRvBlocksCxx.
+// The host launches two geometries (mpcgpu_relax.inc): <1024, 13, 2> and, for the pairs whose records do not fit its 80 KB,
+// <1024, 16, 1> with the CU's 160 KB. Either stages one step at a time: DMA, wait, barrier, merge.
 template <int THREADS, int MAXSLOTS, int WGS, int DIAG = 0, class BLOCKS = MpcRvBlocksAsm>
 __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_var_kernel(RelaxVarParams p)
 {
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_var_kernel
 	const u32 chunk = (p.ntiles + G - 1u) / G;
 
 	for (;;) {
-		__syncthreads(); // the previous tile is done with the pair table and the staging buffers
+		__syncthreads(); // the previous tile is done with the pair table and the staging buffer
 		if (tid == 0) {
 			u32 got = 0xffffffffu;
 			for (u32 k = 0; k < G && got == 0xffffffffu; ++k) {
@@ -204,13 +204,13 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_var_kernel
 		const u32 tab_a = lane < MPC_RV_YLANE ? x0 + (lane < nx ? lane : nx) : ys + (lane - MPC_RV_YLANE < nys ? lane - MPC_RV_YLANE : nys);
 		const u32 *tab_src = s.rec_off + tab_a; // + Z*n per step (rec_off has n*n+1 entries: the run ends are in range)
 		auto load_table = [&](u32 Z) -> u32 { return tab_src[(u64)Z * n]; };
-		// Issues the DMA of the step whose table is `tab` into staging buffer `buf`: the X run, then the Y run, as they lie in
+		// Issues the DMA of the step whose table is `tab` into the staging buffer: the X run, then the Y run, as they lie in
 		// HBM, in chunks of 64 blocks = 1 KiB dealt round-robin to the waves. Returns the register that holds in lane i the LDS
 		// byte address of record i (X run) / in lane 8+j that of record j of the Y run.
-		auto issue_dma = [&](u32 tab, u32 buf) -> u32 {
+		auto issue_dma = [&](u32 tab) -> u32 {
 			const u32 xs = mpc_read_lane(tab, 0u), xe = mpc_read_lane(tab, nx);
 			const u32 yb = mpc_read_lane(tab, MPC_RV_YLANE), ye = mpc_read_lane(tab, MPC_RV_YLANE + nys);
-			const u32 at = MPC_RV_TAB_BYTES + buf * p.buf_bytes; // byte offset of the buffer in the dynamic LDS
+			const u32 at = MPC_RV_TAB_BYTES; // byte offset of the buffer in the dynamic LDS (after the pair table)
 			const u32 xlen = xe - xs;
 			{
 				for (u32 c0 = wave * 64u; c0 < xlen; c0 += NWAVES * 64u) {
@@ -230,14 +230,8 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_var_kernel
 			return lds0 + at + 16u * rel;
 		};
 
-		u32 tab_nxt = 0;
-		u32 vbase_cur = 0, vbase_nxt = 0; // lane i: LDS byte address of record i of the step being merged / being staged
-		if (p.nbuf == 2) {
-			const u32 tab0 = load_table(0);
-			vbase_cur = issue_dma(tab0, 0);
-			if (n > 1) tab_nxt = load_table(1);
-			mpc_dma_wait();
-		} else tab_nxt = load_table(0);
+		u32 tab_nxt = load_table(0);
+		u32 vbase_cur = 0; // lane i: LDS byte address of record i of the step being merged
 		for (u32 Z = 0; Z < n; ++Z) {
 			if (DIAG == 2 && Z > 0) {
 				// measurement only: every step merges step 0's records
@@ -246,15 +240,9 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_var_kernel
 				// waiting for each other, without the staging)
 				__syncthreads();
 				__syncthreads();
-			} else if (p.nbuf == 2) {
-				__syncthreads(); // step Z's records have landed (every wave waited for its own DMA) and step Z-1's readers are done
-				if (DIAG != 2 && Z + 1 < n) {
-					vbase_nxt = issue_dma(tab_nxt, (Z + 1) & 1u);
-					if (Z + 2 < n) tab_nxt = load_table(Z + 2);
-				}
 			} else {
 				__syncthreads(); // step Z-1's readers are done
-				vbase_cur = issue_dma(tab_nxt, 0);
+				vbase_cur = issue_dma(tab_nxt);
 				if (Z + 1 < n) tab_nxt = load_table(Z + 1);
 				mpc_dma_wait();
 				__syncthreads();
@@ -287,10 +275,6 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_var_kernel
 				};
 				slot(slot, std::integral_constant<int, 0>{});
 				blk.drain(); // the last slot's look-ahead reads land before v24..v39 can mean anything else
-			}
-			if (p.nbuf == 2 && DIAG != 2) {
-				mpc_dma_wait(); // my part of step Z+1's records is in LDS
-				if (Z + 1 < n) vbase_cur = vbase_nxt;
 			}
 		}
 		// ---- UpdateFromPost (mysparsemx.cpp:87-113): P' = acc / N on the frozen pattern

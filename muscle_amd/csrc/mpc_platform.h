@@ -164,7 +164,7 @@ __device__ __forceinline__ MpcQuad mpc_lds_load16(unsigned addr)
 	return q;
 }
 // ---- relax_var_kernel's merge of one (cell, Z), hand-scheduled (kernels_relaxv.h holds the C++ statement of the same merge:
-// MpcRvBlocksCxx — what the emulator runs and what MPCGPU_RELAX_MERGE=cxx selects on the device for A/B).
+// MpcRvBlocksCxx — what the emulator runs and what MPCGPU_RELAX_MERGE=cxx selects for relax_band_kernel on the device for A/B).
 // Two sets of 2 x 4 VGPRs hold the blocks {p0, p1, c0 | dist << 16, c1} of the two rows: the set of the slot being merged and
 // the set the NEXT slot's first blocks are read into meanwhile. ds_read_b128 wants register quadruples and the arithmetic
 // wants their single registers, which inline asm can only name when the quadruples are physical registers: v[24:39].

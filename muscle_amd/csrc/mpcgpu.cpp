@@ -162,14 +162,13 @@ struct mpcgpu_ctx {
 	DevBuf d_rec_off, d_sizes, d_tilefit;
 	u32 var_max_rec_blocks = 0;  // largest record, 16-byte blocks
 	u64 var_total_blocks = 0;
-	u32 var_threads = 1024, var_nbuf = 2, var_buf_bytes = 0;
 	std::string store_desc, tiles_desc, relax_kernel_name; // mpcgpu_relax_info
 	bool relax_fallback = false;
 	// tile list of the LDS-tiled relax, cached per pair range (the sparsity pattern is frozen)
 	std::vector<u32> h_tiles;
-	std::vector<u32> h_tiles2; // tiles of the pairs that only fit the one-workgroup-per-CU geometry (var_mixed)
+	std::vector<u32> h_tiles2; // tiles of the pairs that only fit relax_var's fallback geometry (var_mixed)
 	DevBuf d_tiles2;
-	bool var_mixed = false;    // two launches per relax: the configured geometry + 1 x 1024 threads / 160 KB for what does not fit it
+	bool var_mixed = false;    // two launches per relax: the primary geometry + the fallback (1 x 1024 threads / 160 KB) for what does not fit it
 	u64 tiles_k0 = ~0ull, tiles_k1 = ~0ull;
 	u32 tiles_bx = 0, tiles_by = 0;
 	// band tiles (relax_band_kernel, kernels_relaxb.h): band tables of the store, the tile list of the cached pair range

@@ -2,105 +2,74 @@
 // and the launches of relax_var_kernel / relax_band_kernel (kernels_relaxv.h, kernels_relaxb.h). Reference: MPCFlat::ConsIter,
 // consflat.cpp:5-23; ConsPair, conspairflat.cpp:10-110.
 // ---- variable-size records + relax_var_kernel (kernels_relaxv.h) -------------------------------------------------------
-// LDS of one workgroup: the pair table + nbuf staging buffers. 1024-thread workgroups own the CU's 160 KB, 512-thread ones
-// run two per CU.
-void var_lds_geometry(u32 geo, u32 nbuf, u32 *buf_bytes, size_t *smem)
+// Two geometries. The primary one: two 1024-thread workgroups per CU (8 waves per SIMD, 64 VGPRs), 80 KB of LDS each (one
+// workgroup's staging overlaps the other's merges), 13 cells per lane. With 14 the compiler keeps five row-offset registers in
+// spill slots and reloads them inside the walk (each reload waits for vmcnt(0)); 13 has none, and although 2 600 more 4x4 tiles
+// then split into 4x2 the two iterations at 1000 x L~400 take 1171 ms against 1195 (12: 1282, most tiles split) — profiles/r05g.
+// The fallback, for the pairs whose records or cells do not fit that: one 1024-thread workgroup per CU with the CU's 160 KB and
+// 16 cells per lane (second launch). Either has ONE staging buffer after the pair table. (Measured and removed: two 512- or
+// 768-thread workgroups per CU, one 1024-thread workgroup with two staging buffers — docs/HISTORY.md, profiles/r02e, r03b, r04a.)
+u32 var_max_slots(bool fallback) { return fallback ? 16u : 13u; }
+// bytes of the staging buffer. MPCGPU_RELAX_LDS_KB: tests shrink the budget to reach tile splitting with short sequences (_1024: the fallback alone)
+u32 var_buf_bytes(bool fallback)
 {
-	// MPCGPU_RELAX_LDS_KB: tests shrink the budget to reach tile splitting with short sequences (_1024: the one-workgroup geometry alone)
-	const u64 lds_cap = (u64)(geo == 1024 ? env_int("MPCGPU_RELAX_LDS_KB_1024", env_int("MPCGPU_RELAX_LDS_KB", 160)) : env_int("MPCGPU_RELAX_LDS_KB", 80)) * 1024;
-	*buf_bytes = (u32)(((lds_cap - MPC_RV_TAB_BYTES) / nbuf) & ~15ull);
-	*smem = MPC_RV_TAB_BYTES + (size_t)nbuf * *buf_bytes;
+	const u64 lds_cap = (u64)(fallback ? env_int("MPCGPU_RELAX_LDS_KB_1024", env_int("MPCGPU_RELAX_LDS_KB", 160)) : env_int("MPCGPU_RELAX_LDS_KB", 80)) * 1024;
+	return (u32)((lds_cap - MPC_RV_TAB_BYTES) & ~15ull);
 }
 
-// workgroup sizes of relax_var_kernel: 1024 (one per CU), or two per CU of 512 / 640 / 768 threads (4 / 5 / 6 waves per SIMD:
-// 128 / 96 / 80 VGPRs); slots = cells per lane a tile may need (about 12.7 k wave-aligned cells per 4x4 tile at L~400)
-// geometry id = threads per workgroup, except 2048 = two 1024-thread workgroups per CU (8 waves per SIMD, 64 VGPRs)
-// cells per lane of the default geometry (two 1024-thread workgroups per CU, 64 VGPRs): 13. With 14 the compiler keeps five row-offset
-// registers in spill slots and reloads them inside the walk (each reload waits for vmcnt(0)); 13 has none, and although 2 600 more
-// 4x4 tiles then split into 4x2 the two iterations at 1000 x L~400 take 1171 ms against 1195 (12: 1282, most tiles split) — profiles/r05g
-u32 var_slots_2048() { return 13u; } // (12 and 14 were measured and are gone: profiles/r05g)
-u32 var_max_slots(u32 geo) { return geo == 1024 ? 16u : geo == 2048 ? var_slots_2048() : geo == 768 ? 18u : 26u; }
-u32 var_geo_from_env()
+// the instantiation a launch runs: its address (attributes, occupancy), launched when `go`
+template <int SL, int WGS, int DG = 0> const void *relax_var_go(bool go, const RelaxVarParams &rp, u32 grid, size_t smem, hipStream_t st)
 {
-	// default: two 1024-thread workgroups per CU (8 waves per SIMD, 64 VGPRs, 13 cells per lane: var_slots_2048). Round 2 (profiles/r02e, r02h):
-	// 768 x 2 1748 ms per two iterations at 1000 x L~400 against 1984 (512 x 2), 2017 (1024 x 2: spills in the walk), 2060 (1024 x 1,
-	// two staging buffers). With round 3's walk (no spills at 64 VGPRs) 1024 x 2 is level or ahead: 1192 against 1203 ms (768 x 2)
-	// on the synthetic family, 12.45 against 12.94 s on real data (profiles/r04a, r04e)
-	const int t = env_int("MPCGPU_RELAX_WG", 2048);
-	return t == 512 ? 512u : t == 1024 ? 1024u : t == 768 ? 768u : 2048u;
+	if (go) MPC_LAUNCH((relax_var_kernel<1024, SL, WGS, DG>), grid, 1024, smem, st, rp);
+	return (const void *)relax_var_kernel<1024, SL, WGS, DG>;
 }
 
-template <int TH, int SL, int WGS, int DG = 0, class BL = MpcRvBlocksAsm> void launch_relax_var(const RelaxVarParams &rp, u32 grid, size_t smem, hipStream_t st)
+// launches relax_var_kernel of the primary geometry or the fallback over a tile list; `report`: the launch names the kernel in
+// relax_info (and may be a measurement kernel)
+static int relax_var_launch(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1, bool fallback, const DevBuf &d_tiles, u32 ntiles, bool report)
 {
-	auto kern = relax_var_kernel<TH, SL, WGS, DG, BL>;
-	MPC_LAUNCH(kern, grid, TH, smem, st, rp);
-}
-
-// launches relax_var_kernel of geometry `geo` (see var_max_slots) over a tile list
-static int relax_var_launch(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1, u32 geo, u32 nbuf, const DevBuf &d_tiles, u32 ntiles,
-	u32 counter_slot, bool primary)
-{
-	const u32 threads = geo == 2048 ? 1024u : geo;
-	u32 buf_bytes = 0;
-	size_t smem = 0;
-	var_lds_geometry(geo, nbuf, &buf_bytes, &smem);
+	const u32 buf_bytes = var_buf_bytes(fallback);
+	const size_t smem = MPC_RV_TAB_BYTES + (size_t)buf_bytes;
 	RelaxVarParams rp;
 	rp.s = sp; rp.tiles = d_tiles.as<u32>(); rp.ntiles = ntiles;
-	rp.k0 = k0; rp.k1 = k1; rp.nbuf = nbuf; rp.buf_bytes = buf_bytes;
-	rp.tile_next = c->d_tile_next.as<u32>() + 8 * counter_slot;
+	rp.k0 = k0; rp.k1 = k1;
+	rp.tile_next = c->d_tile_next.as<u32>() + (fallback ? 8 : 0);
 	// MPCGPU_RELAX_DIAG=1|2|3 (staging only / merges only / merges + barriers): measurement kernels whose results are WRONG by design;
 	// they exist only in a library built with -DMPC_RELAX_DIAG_BUILD (make diag), which also says so on stderr at every launch
-	int diag = primary ? env_int("MPCGPU_RELAX_DIAG", 0) : 0;
+	int diag = report ? env_int("MPCGPU_RELAX_DIAG", 0) : 0;
 #ifndef MPC_RELAX_DIAG_BUILD
 	if (diag) return fail(c, "MPCGPU_RELAX_DIAG needs a library built with -DMPC_RELAX_DIAG_BUILD (measurement kernels: wrong results by design)");
 #else
 	if (diag) { fprintf(stderr, "[mpcgpu] WARNING: MPCGPU_RELAX_DIAG=%d: measurement kernel, the relax results are WRONG by design\n", diag); c->relax_fallback = true; }
 #endif
-	const char *merge_env = getenv("MPCGPU_RELAX_MERGE"); // "cxx": the compiler's code for the merge instead of the hand-scheduled one (A/B, 768 geometry)
-	const bool merge_cxx = merge_env && !strcmp(merge_env, "cxx");
-	const void *fn = geo == 1024 ? (const void *)relax_var_kernel<1024, 16, 1>
+	if (fallback) diag = 0; // (the measurement kernels are of the primary geometry)
+	u32 grid = 1;
+	auto go = [&](bool launch) -> const void * {
+		if (fallback) return relax_var_go<16, 1>(launch, rp, grid, smem, c->stream);
 #ifdef MPC_RELAX_DIAG_BUILD
-	               : geo == 2048 && diag ? (diag == 1 ? (const void *)relax_var_kernel<1024, 13, 2, 1> : diag == 2 ? (const void *)relax_var_kernel<1024, 13, 2, 2> : (const void *)relax_var_kernel<1024, 13, 2, 3>)
-	               : geo == 768 && diag ? (diag == 1 ? (const void *)relax_var_kernel<768, 18, 2, 1> : diag == 2 ? (const void *)relax_var_kernel<768, 18, 2, 2> : (const void *)relax_var_kernel<768, 18, 2, 3>)
+		if (diag == 1) return relax_var_go<13, 2, 1>(launch, rp, grid, smem, c->stream);
+		if (diag == 2) return relax_var_go<13, 2, 2>(launch, rp, grid, smem, c->stream);
+		if (diag) return relax_var_go<13, 2, 3>(launch, rp, grid, smem, c->stream);
 #endif
-	               : geo == 2048 ? (var_slots_2048() == 14 ? (const void *)relax_var_kernel<1024, 14, 2> : var_slots_2048() == 12 ? (const void *)relax_var_kernel<1024, 12, 2> : (const void *)relax_var_kernel<1024, 13, 2>)
-	               : geo == 768 ? (merge_cxx ? (const void *)relax_var_kernel<768, 18, 2, 0, MpcRvBlocksCxx> : (const void *)relax_var_kernel<768, 18, 2>)
-	               : (const void *)relax_var_kernel<512, 26, 2>;
+		return relax_var_go<13, 2>(launch, rp, grid, smem, c->stream);
+	};
+	const void *fn = go(false);
 	HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-	if (primary) {
+	if (report) {
 		char kn[128];
-		snprintf(kn, sizeof(kn), "relax_var_kernel<%u, %u, %d, %d, %s>", threads, geo == 1024 ? 16u : geo == 2048 ? var_slots_2048() : geo == 768 ? 18u : 26u,
-			geo == 1024 ? 1 : 2, (geo == 768 || geo == 2048) ? diag : 0, (geo == 768 && merge_cxx && !diag) ? "MpcRvBlocksCxx" : "MpcRvBlocksAsm");
+		snprintf(kn, sizeof(kn), "relax_var_kernel<1024, %u, %d, %d, MpcRvBlocksAsm>", var_max_slots(fallback), fallback ? 1 : 2, diag);
 		c->relax_kernel_name = kn;
 	}
 	int occ = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)threads, smem) != hipSuccess || occ < 1) occ = 1;
-	u32 grid = std::max(std::min<u32>(rp.ntiles, (u32)c->prop.multiProcessorCount * (u32)occ), 1u);
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 1024, smem) != hipSuccess || occ < 1) occ = 1;
+	grid = std::max(std::min<u32>(rp.ntiles, (u32)c->prop.multiProcessorCount * (u32)occ), 1u);
 	if (trace_on()) {
-		fprintf(stderr, "[mpcgpu] relax var: tiles=%u wg=%u (geometry %u) nbuf=%u buf=%u B lds=%zu B occ=%d grid=%u max_nnz=%u\n", rp.ntiles, threads, geo, nbuf, buf_bytes, smem, occ, grid, c->max_nnz);
+		fprintf(stderr, "[mpcgpu] relax var: tiles=%u %s buf=%u B lds=%zu B occ=%d grid=%u max_nnz=%u\n", rp.ntiles, fallback ? "fallback" : "primary", buf_bytes, smem, occ, grid, c->max_nnz);
 		fflush(stderr);
 	}
 	TimedSpan ts;
 	if (span_begin(c, 3, &ts)) return 1;
-	if (geo == 1024) launch_relax_var<1024, 16, 1>(rp, grid, smem, c->stream);
-#ifdef MPC_RELAX_DIAG_BUILD
-	else if (geo == 2048 && diag == 1) launch_relax_var<1024, 13, 2, 1>(rp, grid, smem, c->stream);
-	else if (geo == 2048 && diag == 2) launch_relax_var<1024, 13, 2, 2>(rp, grid, smem, c->stream);
-	else if (geo == 2048 && diag == 3) launch_relax_var<1024, 13, 2, 3>(rp, grid, smem, c->stream);
-	else if (geo == 768 && diag == 1) launch_relax_var<768, 18, 2, 1>(rp, grid, smem, c->stream);
-	else if (geo == 768 && diag == 2) launch_relax_var<768, 18, 2, 2>(rp, grid, smem, c->stream);
-	else if (geo == 768 && diag == 3) launch_relax_var<768, 18, 2, 3>(rp, grid, smem, c->stream);
-#endif
-	else if (geo == 2048) {
-		if (var_slots_2048() == 14) launch_relax_var<1024, 14, 2>(rp, grid, smem, c->stream);
-		else if (var_slots_2048() == 12) launch_relax_var<1024, 12, 2>(rp, grid, smem, c->stream);
-		else launch_relax_var<1024, 13, 2>(rp, grid, smem, c->stream);
-	}
-	else if (geo == 768) {
-		if (merge_cxx) launch_relax_var<768, 18, 2, 0, MpcRvBlocksCxx>(rp, grid, smem, c->stream);
-		else launch_relax_var<768, 18, 2>(rp, grid, smem, c->stream);
-	}
-	else launch_relax_var<512, 26, 2>(rp, grid, smem, c->stream);
+	go(true);
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts)) return 1;
 	return 0;
@@ -124,18 +93,18 @@ constexpr u32 kBandThreads = 1024, kBandSlots = 13; // two 1024-thread workgroup
 int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 {
 	const u32 n = c->n, nb1 = c->band_nb1;
-	// geometry: 2 x 1024 threads per CU (default) or 4 x 512 (MPCGPU_RELAX_WG=512): 8 waves per SIMD either way; a barrier of the
-	// walk then holds 8 waves instead of 16, and three other workgroups fill a waiting one's issue slots
-	const u32 bthreads = env_int("MPCGPU_RELAX_WG", 1024) == 512 ? 512u : 1024u;
+	// geometry: two 1024-thread workgroups per CU, 80 KB of LDS each (kBandThreads). (Measured and removed: four 512-thread workgroups
+	// per CU with 40 KB each, whose barriers hold 8 waves instead of 16: 9.6 of 13 cells per lane at 1000 x L~400, and 2472 against
+	// 1545 ms per two iterations on rdrp-500 — profiles/r06g, r10a)
 	// (measured and removed again, profiles/r10a_rdrp_geometry_sweep.log: ONE 1024-thread workgroup per CU with the CU's 160 KB and 26 cells per
 	// lane — 8x4 bands, 10.7 cells per lane, every step prefetched, 6.6 B per cell-step instead of 11.7 — is 18 % SLOWER on real data
 	// (rdrp-500: 1818 against 1545 ms per two iterations): the walk's merges are chains of dependent LDS reads and want 8 waves per SIMD)
-	const u32 lds_bytes = (u32)std::max(env_int("MPCGPU_RELAX_LDS_KB", bthreads == 512 ? 40 : 80), 3) * 1024u;
+	const u32 lds_bytes = (u32)std::max(env_int("MPCGPU_RELAX_LDS_KB", 80), 3) * 1024u;
 	const u32 cap = (lds_bytes - MPC_RB_TAB_BYTES) & ~15u, cap_blocks = cap / 16;
 	const u32 cus = (u32)c->prop.multiProcessorCount;
-	// the direct-index merge (window records for the Y operand) where the store has them; the 512-thread geometry and the
-	// measurement kernels exist for the block walk only
-	const bool use_win = c->win_ok && bthreads == 1024 && !env_int("MPCGPU_RELAX_DIAG", 0);
+	// the direct-index merge (window records for the Y operand) where the store has them; the measurement kernels exist for the
+	// block walk only
+	const bool use_win = c->win_ok && !env_int("MPCGPU_RELAX_DIAG", 0);
 	const u32 kernel_slots = use_win ? kBandSlotsWin : kBandSlots;
 	const u32 max_slots = (u32)std::min<int>(std::max(env_int("MPCGPU_RELAX_SLOTS", (int)kernel_slots), 1), (int)kernel_slots);
 	if (c->btiles_k0 != k0 || c->btiles_k1 != k1) {
@@ -144,7 +113,7 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 		auto lap_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_cut0).count(); };
 		RbTileTabs tb;
 		tb.cell_off = c->d_cell_off.as<u32>(); tb.yr = c->d_yr.as<u32>(); tb.ovf_sum = c->d_ovf_sum.as<u32>(); tb.ovf_maxc = c->d_ovf_maxc.as<u32>();
-		tb.nb1 = nb1; tb.threads = bthreads; tb.k0 = k0; tb.k1 = k1;
+		tb.nb1 = nb1; tb.threads = kBandThreads; tb.k0 = k0; tb.k1 = k1;
 		tb.win = use_win ? 1u : 0u;
 		tb.ysum = use_win ? c->d_wsum.as<u32>() : tb.ovf_sum; tb.ymaxc = use_win ? c->d_wmaxc.as<u32>() : tb.ovf_maxc;
 		// tile words of a list of tiles whose words 0..5 are set: Y ranges, first-piece blocks, slots; out: slots, mean blocks, bound, cells
@@ -229,7 +198,7 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 			Score sc = {0, 0, 0, out.size() / 4};
 			u64 cells = 0, est = 0, ok = 0;
 			for (size_t t = 0; t + 3 < out.size(); t += 4) { cells += out[t + 3]; est += out[t + 1]; ok += out[t + 1] <= target ? 1 : 0; }
-			if (sc.tiles) { sc.fill = (double)cells / ((double)sc.tiles * max_slots * bthreads); sc.in_target = (double)ok / (double)sc.tiles; }
+			if (sc.tiles) { sc.fill = (double)cells / ((double)sc.tiles * max_slots * kBandThreads); sc.in_target = (double)ok / (double)sc.tiles; }
 			sc.bytes_per_cell = cells ? 16.0 * (double)est / (double)cells : 0.0;
 			return sc;
 		};
@@ -442,7 +411,7 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 			char b[384];
 			snprintf(b, sizeof(b), "%zu band tiles of <= %ux%u pairs (%llu split), target %u B per step of %u B staging (%s), mean step %.0f B, %.1f of %u cells per lane (%.2f slots on the busiest wave), %.2f B per cell-step",
 				nt, use_nx, use_ny, (unsigned long long)nsplit, use_target * 16, cap, use_target <= cap_blocks / 2 ? "two steps resident" : "one step resident",
-				nt ? 16.0 * (double)est / (double)nt : 0.0, nt ? (double)cells / ((double)nt * bthreads) : 0.0, max_slots, nt ? (double)slots / (double)nt : 0.0, cells ? 16.0 * (double)est / (double)cells : 0.0);
+				nt ? 16.0 * (double)est / (double)nt : 0.0, nt ? (double)cells / ((double)nt * kBandThreads) : 0.0, max_slots, nt ? (double)slots / (double)nt : 0.0, cells ? 16.0 * (double)est / (double)cells : 0.0);
 			c->tiles_desc = b;
 		}
 		c->h_btiles.swap(okw);
@@ -492,7 +461,6 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 			if (merge_cxx) { fn = (const void *)relax_band_kernel<kBandThreads, kBandSlotsWin, 2, 0, MpcRbWinCxx>; if (go) MPC_LAUNCH((relax_band_kernel<kBandThreads, kBandSlotsWin, 2, 0, MpcRbWinCxx>), grid, kBandThreads, smem, c->stream, rp); }
 			else { fn = (const void *)relax_band_kernel<kBandThreads, kBandSlotsWin, 2, 0, MpcRbWinAsm>; if (go) MPC_LAUNCH((relax_band_kernel<kBandThreads, kBandSlotsWin, 2, 0, MpcRbWinAsm>), grid, kBandThreads, smem, c->stream, rp); }
 		}
-		else if (bthreads == 512) { fn = (const void *)relax_band_kernel<512, kBandSlots, 4>; if (go) MPC_LAUNCH((relax_band_kernel<512, kBandSlots, 4>), grid, 512, smem, c->stream, rp); }
 		else
 		MPC_RB_DIAG_CASES(kBandThreads, kBandSlots)
 		if (merge_cxx) { fn = (const void *)relax_band_kernel<kBandThreads, kBandSlots, 2, 0, MpcRbBlocksCxx>; if (go) MPC_LAUNCH((relax_band_kernel<kBandThreads, kBandSlots, 2, 0, MpcRbBlocksCxx>), grid, kBandThreads, smem, c->stream, rp); }
@@ -504,13 +472,13 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 			if (c->band_fn == fn && c->band_smem == smem) occ = c->band_occ;
 			else {
 				HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-				if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)bthreads, smem) != hipSuccess || occ < 1) occ = 1;
+				if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)kBandThreads, smem) != hipSuccess || occ < 1) occ = 1;
 				c->band_fn = fn; c->band_smem = smem; c->band_occ = occ;
 			}
 			grid = std::max(std::min<u32>(ntiles, cus * (u32)occ), 1u);
 			char kn[128];
-			snprintf(kn, sizeof(kn), "relax_band_kernel<%u, %u, %u, %d, %s>", bthreads, kernel_slots, bthreads == 512 ? 4u : 2u, bthreads == 512 ? 0 : diag,
-				use_win ? (merge_cxx ? "MpcRbWinCxx" : "MpcRbWinAsm") : merge_cxx && !diag && bthreads == 1024 ? "MpcRbBlocksCxx" : "MpcRbBlocksAsm");
+			snprintf(kn, sizeof(kn), "relax_band_kernel<%u, %u, 2, %d, %s>", kBandThreads, kernel_slots, diag,
+				use_win ? (merge_cxx ? "MpcRbWinCxx" : "MpcRbWinAsm") : merge_cxx && !diag ? "MpcRbBlocksCxx" : "MpcRbBlocksAsm");
 			c->relax_kernel_name = kn;
 			if (trace_on()) { fprintf(stderr, "[mpcgpu] relax band: %s; lds=%zu B occ=%d grid=%u\n", c->tiles_desc.c_str(), smem, occ, grid); fflush(stderr); }
 		} else {
@@ -540,16 +508,14 @@ int relax_var(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 {
 	const u32 n = c->n;
 	auto pidx = [&](u32 i, u32 j) { return pair_pos(c, i, j); };
-	// Tiles of geometry (geo, nbuf) out of a list of candidate tiles: a tile is kept when its cells fit the register slots and its
+	// Tiles of the primary geometry or the fallback out of a list of candidate tiles: a tile is kept when its cells fit the register slots and its
 	// records of one step, packed back to back, fit one staging buffer at EVERY step (the worst step of every tile is measured on
 	// the device); others are split (Y first, then X) and measured again. Single pairs that still do not fit go to `leftover`
-	// (when given: the second geometry takes them) or fail the call.
-	auto build_tiles = [&](u32 geo, u32 nbuf, std::vector<u32> cand, std::vector<u32> &ok, std::vector<u32> *leftover) -> int {
-		const u32 threads = geo == 2048 ? 1024u : geo;
-		u32 buf_bytes = 0;
-		size_t smem = 0;
-		var_lds_geometry(geo, nbuf, &buf_bytes, &smem);
-		const u32 max_slots = (u32)std::min<int>(std::max(env_int("MPCGPU_RELAX_SLOTS", (int)var_max_slots(geo)), 1), (int)var_max_slots(geo));
+	// (when given: the fallback takes them) or fail the call.
+	auto build_tiles = [&](bool fallback, std::vector<u32> cand, std::vector<u32> &ok, std::vector<u32> *leftover) -> int {
+		const u32 threads = 1024;
+		const u32 buf_bytes = var_buf_bytes(fallback);
+		const u32 max_slots = (u32)std::min<int>(std::max(env_int("MPCGPU_RELAX_SLOTS", (int)var_max_slots(fallback)), 1), (int)var_max_slots(fallback));
 		// slots a tile needs: the cells of its pairs in [k0,k1), every pair rounded up to whole waves, in chunks of `threads`
 		auto tile_slots = [&](u32 x0, u32 nx, u32 y0, u32 ny) {
 			u64 cells = 0;
@@ -627,8 +593,8 @@ int relax_var(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 						cand.insert(cand.end(), {x0, nx, y0, ny});
 					}
 		std::vector<u32> ok, ok2, left;
-		if (build_tiles(c->var_threads, c->var_nbuf, cand, ok, c->var_mixed ? &left : nullptr)) return 1;
-		if (!left.empty() && build_tiles(1024, 1, left, ok2, nullptr)) return 1;
+		if (build_tiles(false, cand, ok, c->var_mixed ? &left : nullptr)) return 1;
+		if (!left.empty() && build_tiles(true, left, ok2, nullptr)) return 1;
 		c->tiles_desc = describe(ok);
 		if (!ok2.empty()) c->tiles_desc += "; + 1 x 1024-thread workgroup per CU, 1 staging buffer of 160 KB for " + describe(ok2);
 		c->h_tiles.swap(ok);
@@ -641,8 +607,8 @@ int relax_var(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 	if (c->h_tiles.empty() && c->h_tiles2.empty()) return 0;
 	HIPCHK(c, c->d_tile_next.ensure(16 * 4));
 	HIPCHK(c, hipMemsetAsync(c->d_tile_next.p, 0, 16 * 4, c->stream));
-	if (!c->h_tiles.empty() && relax_var_launch(c, sp, k0, k1, c->var_threads, c->var_nbuf, c->d_tiles, (u32)(c->h_tiles.size() / 4), 0, true)) return 1;
-	if (!c->h_tiles2.empty() && relax_var_launch(c, sp, k0, k1, 1024, 1, c->d_tiles2, (u32)(c->h_tiles2.size() / 4), 1, c->h_tiles.empty())) return 1;
+	if (!c->h_tiles.empty() && relax_var_launch(c, sp, k0, k1, false, c->d_tiles, (u32)(c->h_tiles.size() / 4), true)) return 1;
+	if (!c->h_tiles2.empty() && relax_var_launch(c, sp, k0, k1, true, c->d_tiles2, (u32)(c->h_tiles2.size() / 4), c->h_tiles.empty())) return 1;
 	return 0;
 }
 

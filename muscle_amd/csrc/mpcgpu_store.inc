@@ -6,12 +6,6 @@ int build_var_store(mpcgpu_ctx *c)
 {
 	const u32 n = c->n;
 	if (c->max_len > MPC_RV_MAXLEN) return 2;
-	// geometry: the configured one (default two 768-thread workgroups per CU, 80 KB of LDS each); when the largest pair does not
-	// fit it — long or poorly aligned sequences: wide posterior rows, records of tens of KB — one 1024-thread workgroup per CU
-	// with the whole 160 KB as ONE staging buffer, before giving the run to the fallback layouts
-	u32 threads = var_geo_from_env(); // geometry id (see var_max_slots)
-	u32 nbuf = (u32)std::min(std::max(env_int("MPCGPU_RELAX_NBUF", threads == 1024 ? 2 : 1), 1), 2);
-	auto slots_ok = [&](u32 geo) { return (((u64)c->max_nnz + 63) & ~63ull) <= (u64)var_max_slots(geo) * (geo == 2048 ? 1024u : geo); };
 	StoreParams sp0;
 	fill_store_params(c, sp0);
 	const u64 nn = (u64)n * n;
@@ -33,37 +27,24 @@ int build_var_store(mpcgpu_ctx *c)
 		off[b + 1] = (u32)run;
 	}
 	if (max_rec > 4095u) return 2; // a block's distance field holds 16 bits of bytes
-	u32 buf_bytes = 0;
-	size_t smem = 0;
-	var_lds_geometry(threads, nbuf, &buf_bytes, &smem);
-	c->var_mixed = false;
+	// whole-record tiles of relax_var_kernel (mpcgpu_relax.inc): the primary geometry (two 1024-thread workgroups per CU, 80 KB of
+	// LDS each), plus a second launch of the fallback (one 1024-thread workgroup per CU with the whole 160 KB) for the pairs that do
+	// not fit it — long or poorly aligned sequences: wide posterior rows, records of tens of KB (such runs end up with tiles of one
+	// pair: two records of 20..40 KB per step for ~3 slots of cells); when a pair fits neither, not for whole-record tiles
+	auto fits = [&](bool fallback) { // every single pair: its two records, and its cells
+		return 2ull * max_rec * 16 <= var_buf_bytes(fallback) && (((u64)c->max_nnz + 63) & ~63ull) <= (u64)var_max_slots(fallback) * 1024u;
+	};
+	const bool fits_primary = fits(false), pairs_ok = fits_primary || fits(true);
 	const char *tiles_mode = getenv("MPCGPU_RELAX_TILES"); // "pairs": whole-record tiles of relax_var_kernel only; "band": band tiles whatever the size
 	// MPCGPU_RELAX_SMALL_PAIRS=<n> (default 0 = never; the drop-in binary sets 40): stores of <= n sequences whose pairs fit the
 	// whole-record tiles take those. A shrub of -super7 (<= 32 sequences, 412 of them in a 10 000-sequence run) is relaxed in 0.3 ms
 	// either way, but the band path builds window records and band tables and cuts its tiles on the device first: 4.6 ms of launches
 	// and round trips per store against 0.06 (profiles/r10d_small_store_time.log) — the 0.7 s that run lost in round 4.
 	const int small_n = env_int("MPCGPU_RELAX_SMALL_PAIRS", 0);
-	const bool small_pairs = small_n > 0 && n <= (u32)small_n && 2ull * max_rec * 16 <= buf_bytes && slots_ok(threads) &&
-		!(tiles_mode && !strcmp(tiles_mode, "band"));
+	const bool small_pairs = small_n > 0 && n <= (u32)small_n && fits_primary && !(tiles_mode && !strcmp(tiles_mode, "band"));
 	const bool want_band = !(tiles_mode && !strcmp(tiles_mode, "pairs")) && !small_pairs && c->npairs < 0xffffffffull;
-	bool pairs_ok = true;
-	if (2ull * max_rec * 16 > buf_bytes || !slots_ok(threads)) { // not every single pair (two records, its cells) fits a tile of this geometry
-		u32 bb1 = 0;
-		size_t sm1 = 0;
-		var_lds_geometry(1024, 1, &bb1, &sm1);
-		if (2ull * max_rec * 16 > bb1 || !slots_ok(1024)) {
-			if (!want_band) return 2;
-			pairs_ok = false; // whole-record tiles are not an option for this run; band tiles may still be (relax_band)
-		}
-		// MPCGPU_RELAX_MIXED (default 1): keep the configured geometry for the pairs that fit it (two workgroups per CU: one's
-		// staging overlaps the other's merges) and give the rest to a second launch of the one-workgroup geometry; 0: everything
-		// to the one-workgroup geometry
-		if (!pairs_ok) {}
-		else if (!(threads == 1024 && nbuf == 1) && env_int("MPCGPU_RELAX_MIXED", 1)) {
-			c->var_mixed = true; // (such runs end up with tiles of one pair: two records of 20..40 KB per step for ~3 slots of cells)
-		}
-		else { threads = 1024; nbuf = 1; buf_bytes = bb1; smem = sm1; }
-	}
+	c->var_mixed = !fits_primary && pairs_ok;
+	if (!pairs_ok && !want_band) return 2; // (with pairs_ok false, band tiles may still be an option: relax_band)
 	const u64 pad_bytes = run * 16 + 4 * std::max<u64>(c->total_entries, 1);
 	size_t freeb = 0, totb = 0;
 	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
@@ -75,16 +56,12 @@ int build_var_store(mpcgpu_ctx *c)
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // (the offsets live in the context: v_off; the wait orders the upload before the kernels that read the table)
 	c->have_pad = true;
 	c->pad_lcap1 = c->max_len;
-	c->var_threads = threads; c->var_nbuf = nbuf; c->var_buf_bytes = buf_bytes;
 	c->var_max_rec_blocks = max_rec; c->var_total_blocks = run;
 	c->tiles_k0 = c->tiles_k1 = ~0ull;
 	{
 		char b[512];
-		snprintf(b, sizeof(b), "variable-size dense records: %u x %u records, %.2f GB, mean %.0f B, largest %u B; relax_var_kernel, %s, %u staging buffer%s of %u B",
-			n, n, (double)run * 16 / 1e9, (double)run * 16 / (double)nn, max_rec * 16,
-			threads == 2048 ? "2 x 1024-thread workgroups per CU" : threads == 1024 ? "1 x 1024-thread workgroup per CU" :
-			threads == 768 ? "2 x 768-thread workgroups per CU" : "2 x 512-thread workgroups per CU",
-			nbuf, nbuf == 1 ? "" : "s", buf_bytes);
+		snprintf(b, sizeof(b), "variable-size dense records: %u x %u records, %.2f GB, mean %.0f B, largest %u B; relax_var_kernel, 2 x 1024-thread workgroups per CU, 1 staging buffer of %u B",
+			n, n, (double)run * 16 / 1e9, (double)run * 16 / (double)nn, max_rec * 16, var_buf_bytes(false));
 		c->store_desc = b;
 		if (c->var_mixed) c->store_desc += " (pairs whose records do not fit it: 1 x 1024-thread workgroup per CU with 160 KB, second launch)";
 		c->tiles_desc.clear(); c->relax_kernel_name.clear(); c->relax_fallback = false;
@@ -116,8 +93,8 @@ int build_var_store(mpcgpu_ctx *c)
 	StoreParams sp;
 	fill_store_params(c, sp);
 	if (trace_on()) {
-		fprintf(stderr, "[mpcgpu] store: variable-size dense records, %u x %u records, %.2f GB (mean %.0f B, largest %u B), wg=%u nbuf=%u\n", n, n,
-			(double)run * 16 / 1e9, (double)run * 16 / (double)nn, max_rec * 16, threads, nbuf);
+		fprintf(stderr, "[mpcgpu] store: variable-size dense records, %u x %u records, %.2f GB (mean %.0f B, largest %u B)%s\n", n, n,
+			(double)run * 16 / 1e9, (double)run * 16 / (double)nn, max_rec * 16, c->var_mixed ? ", relax_var fallback for the largest pairs" : "");
 		fflush(stderr);
 	}
 	TimedSpan ts;

@@ -2,7 +2,7 @@
 SIMT emulator then hands the OS thread to the GPU threads of a block in another order than 0..n-1 (tests/emu/hip_emu.cpp).
 Between two barriers a GPU thread runs uninterrupted, so a missing barrier or any other race inside a barrier interval
 makes the result depend on that order; these scenarios cover every kernel that synchronises through LDS or global
-memory within a workgroup (fb with row blocks, post, pad build, both relax layouts incl. the two-buffer schedule,
+memory within a workgroup (fb with row blocks, post, pad build, both relax layouts incl. both geometries of relax_var_kernel,
 calc_aln, the BuildPost path of align_alns)."""
 import os
 import sys
@@ -31,8 +31,9 @@ def with_env(env, fn):
 def main():
     seqs = make_family(9, 18, seed=5) + [make_family(1, 70, seed=9)[0], "MKV"]
     want = P.run_oracle(seqs)
-    for env in ({}, {"MPCGPU_RELAX_WG": "1024"}, {"MPCGPU_RELAX_WG": "1024", "MPCGPU_RELAX_NBUF": "1"}, {"MPCGPU_RELAX": "gather"},
-                {"MPCGPU_POST": "sort"}, {"MPCGPU_RELAX_WG": "512"}):
+    # relax_var_kernel: whole-record tiles in the primary geometry, and in the 160 KB fallback (a primary budget no pair fits)
+    for env in ({}, {"MPCGPU_RELAX_TILES": "pairs"}, {"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_LDS_KB": "1", "MPCGPU_RELAX_LDS_KB_1024": "160"},
+                {"MPCGPU_RELAX": "gather"}, {"MPCGPU_POST": "sort"}):
         P.assert_same(with_env(env, lambda: P.run_lib(seqs, lib_path=EMU)), want, "order %s %s" % (os.environ.get("EMU_SCHED"), env))
     seqs = [make_family(1, 131, seed=21)[0], make_family(1, 66, seed=22)[0], "MKV"]
     got = with_env({"MPCGPU_FB_LONG_H": "1", "MPCGPU_FB_LONG_MIN": "2"}, lambda: P.run_lib(seqs, lib_path=EMU))

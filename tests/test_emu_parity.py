@@ -377,34 +377,44 @@ def test_emu_one_pair_per_batch(emu):
     P.assert_same(got, P.run_oracle(seqs), "one pair per batch")
 
 
-def test_emu_relax_512_thread_workgroups(emu):
-    seqs = make_family(7, 24, seed=63)
-    got = _with_env({"MPCGPU_RELAX_WG": "512"}, lambda: P.run_lib(seqs, lib_path=emu))
-    P.assert_same(got, P.run_oracle(seqs), "512-thread relax workgroups")
+# relax_var_kernel's two geometries (whole-record tiles): the primary one, and the 160 KB fallback forced by a primary budget of 1 KB
+# that no pair of these sequences fits (the fallback then takes every pair, and its launch names the kernel)
+VAR_PRIMARY = {"MPCGPU_RELAX_TILES": "pairs"}
+VAR_FALLBACK = {"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_LDS_KB": "1", "MPCGPU_RELAX_LDS_KB_1024": "160"}
 
 
-@pytest.mark.parametrize("env", [{"MPCGPU_RELAX_WG": "1024"}, {"MPCGPU_RELAX_WG": "1024", "MPCGPU_RELAX_NBUF": "1"}, {"MPCGPU_RELAX_WG": "2048"},
-                                 {"MPCGPU_RELAX_WG": "512", "MPCGPU_RELAX_NBUF": "2"}, {"MPCGPU_RELAX_SLOTS": "3"}, {"MPCGPU_RELAX_LDS_KB": "6"},
-                                 {"MPCGPU_RELAX_WG": "1024", "MPCGPU_RELAX_LDS_KB": "12"}])
+def _var_kernel(env):
+    """the relax_var_kernel instantiation a run with `env` launches (relax_info's kernel=...)"""
+    return "kernel=relax_var_kernel<1024, %s, 0, MpcRvBlocksAsm>" % ("16, 1" if "MPCGPU_RELAX_LDS_KB_1024" in env else "13, 2")
+
+
+@pytest.mark.parametrize("env", [VAR_PRIMARY, VAR_FALLBACK, dict(VAR_FALLBACK, MPCGPU_RELAX_LDS_KB_1024="12"),
+                                 {"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_LDS_KB": "12"},
+                                 {"MPCGPU_RELAX_SLOTS": "3"}, {"MPCGPU_RELAX_LDS_KB": "6"}])
 def test_emu_relax_var_geometries(emu, env):
-    """relax_var_kernel in its other shapes: one 1024-thread workgroup per CU with two staging buffers (DMA of step Z+1 under the
-    merges of step Z) or one, two 1024- or 512-thread workgroups per CU, a small slot budget and a small LDS (tiles split by
-    the host's per-tile fit check) — all the default's arithmetic, all bit-identical to the oracle."""
+    """relax_var_kernel in its two geometries: two 1024-thread workgroups per CU (80 KB each) and the fallback, one per CU with
+    160 KB (or a small budget); a small LDS (tiles split by the host's per-tile fit check) and a small slot budget — all the
+    default's arithmetic, all bit-identical to the oracle."""
     seqs = make_family(9, 18, seed=5) + [make_family(1, 70, seed=9)[0], "MKV"]
-    got = _with_env(env, lambda: P.run_lib(seqs, lib_path=emu))
+    info = {}
+    got = _with_env(env, lambda: P.run_lib(seqs, lib_path=emu, info=info))
     P.assert_same(got, P.run_oracle(seqs), "relax_var_kernel %s" % env)
+    if "MPCGPU_RELAX_TILES" in env:
+        assert _var_kernel(env) in info["relax_info"], (env, info["relax_info"])
 
 
-@pytest.mark.parametrize("env", [{}, {"MPCGPU_RELAX_WG": "1024"}, {"MPCGPU_RELAX_WG": "1024", "MPCGPU_RELAX_NBUF": "1"}, {"MPCGPU_RELAX_WG": "768"}])
+@pytest.mark.parametrize("env", [{}, VAR_PRIMARY, VAR_FALLBACK])
 def test_emu_relax_staging_with_late_dma(emu, env):
     """EMU_DMA=late: an LDS-DMA transfer poisons its 16 destination bytes when it is issued and delivers them only when the issuing
     thread waits for it (mpc_dma_wait) — as late as the hardware may. A walk that merged a record before the wait + barrier that
-    follows its staging (one staging buffer), or that let step Z+1's transfers into a buffer step Z still reads (two buffers),
-    computes with garbage: the results must still be the oracle's."""
+    follows its staging computes with garbage: the results must still be the oracle's (the default band tiles, and both
+    geometries of relax_var_kernel)."""
     seqs = make_family(9, 18, seed=5) + [make_family(1, 70, seed=9)[0], "MKV"]
-    got = _with_env(dict(env, EMU_DMA="late"), lambda: P.run_lib(seqs, lib_path=emu))
+    info = {}
+    got = _with_env(dict(env, EMU_DMA="late"), lambda: P.run_lib(seqs, lib_path=emu, info=info))
     want = P.run_oracle(seqs)
     P.assert_same(got, want, "late DMA %s" % env)
+    assert (_var_kernel(env) if env else "kernel=relax_band_kernel") in info["relax_info"], (env, info["relax_info"])
     if not env:  # the checker checks: when the waits deliver nothing the same run must NOT reproduce the oracle
         bad = _with_env({"EMU_DMA": "never"}, lambda: P.run_lib(seqs, lib_path=emu))
         with pytest.raises(AssertionError):
@@ -624,8 +634,6 @@ def test_emu_relax_two_geometries(emu):
     got = _with_env({"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_LDS_KB": "1", "MPCGPU_RELAX_LDS_KB_1024": "8"}, run)
     assert "second launch" in info["geo"] and "+ 1 x 1024" in info["geo"], info["geo"]
     P.assert_same(got, want, "two geometries")
-    got0 = _with_env({"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_LDS_KB": "1", "MPCGPU_RELAX_LDS_KB_1024": "8", "MPCGPU_RELAX_MIXED": "0"}, lambda: P.run_lib(seqs, lib_path=emu))
-    P.assert_same(got0, want, "one-workgroup geometry alone")
 
 
 # ---- band tiles (relax_band_kernel, kernels_relaxb.h) ----------------------------------------------------------------------

@@ -283,16 +283,17 @@ def test_relax_gather_equals_tiled():
         del os.environ["MPCGPU_RELAX"]
     P.assert_same(a, b, "gather vs tiled")
     P.assert_same(a, P.run_oracle(seqs), "tiled vs oracle")
-    # relax_band_kernel (the default above) in forced tile shapes and staging modes, with the compiler's merge instead of the
-    # hand-scheduled one (the shipped asm is pinned only here, on hardware: the emulator runs the C++ statement), and in its
-    # four-workgroups-per-CU geometry; relax_var_kernel (whole-record tiles) in its geometries
+    # relax_band_kernel (the default above) in forced tile shapes and staging modes, and with the compiler's merge instead of the
+    # hand-scheduled one (the shipped asm is pinned only here, on hardware: the emulator runs the C++ statement); relax_var_kernel
+    # (whole-record tiles) in its two geometries
     variants = [{"MPCGPU_RELAX_SHAPE": "8,8"}, {"MPCGPU_RELAX_SHAPE": "4,2,12"}, {"MPCGPU_RELAX_SHAPE": "1,1"},
                 {"MPCGPU_RELAX_SHAPE": "8,8", "MPCGPU_RELAX_SLOTS": "2"}, {"MPCGPU_RELAX_LDS_KB": "24"},
-                {"MPCGPU_RELAX_MERGE": "cxx"}, {"MPCGPU_RELAX_WG": "512"}, {"MPCGPU_RELAX_ORDER": "pairs"}, {"MPCGPU_RELAX_ORDER": "pairs", "MPCGPU_RELAX_FORM": "walk"}, {"MPCGPU_RELAX_ORDER": "1"}, {"MPCGPU_RELAX_ORDER": "5", "MPCGPU_RELAX_FORM": "walk"},
+                {"MPCGPU_RELAX_MERGE": "cxx"}, {"MPCGPU_RELAX_ORDER": "pairs"}, {"MPCGPU_RELAX_ORDER": "pairs", "MPCGPU_RELAX_FORM": "walk"}, {"MPCGPU_RELAX_ORDER": "1"}, {"MPCGPU_RELAX_ORDER": "5", "MPCGPU_RELAX_FORM": "walk"},
                 # the default above looks the Y rows up in window records (narrow rows); the two-list walk on block records, and both merges of it
                 {"MPCGPU_RELAX_FORM": "walk"}, {"MPCGPU_RELAX_FORM": "walk", "MPCGPU_RELAX_MERGE": "cxx"}, {"MPCGPU_RELAX_FORM": "walk", "MPCGPU_RELAX_SHAPE": "4,2,12"}]
-    variants += [{"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_WG": geo, "MPCGPU_RELAX_NBUF": nbuf}
-                 for geo, nbuf in (("2048", "1"), ("1024", "2"), ("1024", "1"), ("512", "1"), ("768", "1"))]
+    # the primary geometry (two 1024-thread workgroups per CU, 80 KB each), and the 160 KB fallback forced by a primary budget of 1 KB
+    # that no pair fits (the fallback then takes every pair)
+    variants += [{"MPCGPU_RELAX_TILES": "pairs"}, {"MPCGPU_RELAX_TILES": "pairs", "MPCGPU_RELAX_LDS_KB": "1", "MPCGPU_RELAX_LDS_KB_1024": "160"}]
     for env in variants:
         os.environ.update(env)
         try:
@@ -302,7 +303,9 @@ def test_relax_gather_equals_tiled():
             for k in env:
                 del os.environ[k]
         P.assert_same(a, r, "relax variant %s" % env)
-        assert ("relax_var_kernel" if "MPCGPU_RELAX_TILES" in env else "relax_band_kernel") in info["relax_info"], (env, info["relax_info"])
+        kernel = ("relax_var_kernel<1024, %s, 0, MpcRvBlocksAsm>" % ("16, 1" if "MPCGPU_RELAX_LDS_KB_1024" in env else "13, 2")
+                  if "MPCGPU_RELAX_TILES" in env else "relax_band_kernel<1024, ")
+        assert "kernel=" + kernel in info["relax_info"], (env, info["relax_info"])
 
 
 def test_random_ragged_stores_against_the_oracle():

@@ -72,10 +72,7 @@ def test_default_relax_walk_has_no_spill_reloads(isa, kernel):
     assert not waits, "; ".join(body[k].strip() for k in waits[:5])
 
 
-BAND_512 = "_Z17relax_band_kernelILi512ELi13ELi4ELi0E14MpcRbBlocksAsmEv15RelaxBandParams"  # MPCGPU_RELAX_WG=512: four 512-thread workgroups per CU
-
-
-@pytest.mark.parametrize("kernel", [BAND_WIN, BAND, BAND_512])
+@pytest.mark.parametrize("kernel", [BAND_WIN, BAND])
 def test_band_merge_registers_are_not_touched_between_statements(isa, kernel):
     """The hand-scheduled merge leaves LDS reads in flight into v24..v40 (the next slot's first blocks, its Y bias) when a
     statement ends; the compiler does not know. Between the end of one merge statement and the opening wait of the next
