@@ -90,7 +90,8 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  * those of a few groups only. mpcgpu_set_pair_order makes the context enumerate its pairs rectangle by rectangle (row-major
  * inside each): rects[4 r ..] = {xa, xb, ya, yb} is either off the diagonal (ya >= xb: every (x, y) of [xa,xb) x [ya,yb)) or a
  * triangle (xa == ya, xb == yb: the pairs x < y inside [xa,xb)); together they must hold every pair exactly once. nrects == 0:
- * back to InitPairs order. Call after mpcgpu_set_seqs (which resets it), before stage A.
+ * back to InitPairs order. Call after mpcgpu_set_seqs (which resets it), before stage A. A refused list changes nothing: the
+ * order, shard and store the context had stay as they were.
  * From then on the SHARDING calls — mpcgpu_calc_posteriors, mpcgpu_store_import(_part), mpcgpu_values_slice, mpcgpu_cons_iter —
  * take POSITIONS in this order ("[k0,k1)" = the k0-th to k1-th pair of the enumeration), and the values array is in position
  * order; the RESULT getters (mpcgpu_get_ea, _get_nnz, _get_sparse, _get_sparse_range) and everything that names sequences
@@ -144,6 +145,7 @@ int mpcgpu_store_import(mpcgpu_ctx *ctx, uint32_t nshards, const uint64_t *k0, c
  * matrices (A, Z) of the sequences A that those pairs touch and of no other (the block partition: half of the store at 8 ranks;
  * what a ConsPair of the range reads, conspairflat.cpp:49-89), while everything per pair (packed matrices, values, EA) is
  * complete. mpcgpu_cons_iter outside the range is refused; mpcgpu_cons_commit(_range) commits every entry into what exists.
+ * Shards whose byte ranges [offsets[s], offsets[s] + bytes[s]) overlap are refused before the current store is touched.
  * own = [0, pair_count) is mpcgpu_store_import. */
 int mpcgpu_store_import_part(mpcgpu_ctx *ctx, uint32_t nshards, const uint64_t *k0, const uint64_t *k1, const uint64_t *bytes,
                              const uint64_t *offsets, void *dev_all, uint64_t own_k0, uint64_t own_k1);
@@ -225,7 +227,9 @@ int mpcgpu_align_alns_w(mpcgpu_ctx *ctx, uint32_t n1, const uint32_t *seq1, uint
  * with n2[j] rows, C1[j] x C2[j] columns; seqs holds the sequence indices of its rows, MSA1's then MSA2's, the joins back to back;
  * pos2col likewise the rows' position -> column maps. All weights are 1.0f (what MPCFlat::Run sets, mpcflat.cpp:324).
  * paths: njoins slots of path_stride bytes (>= C1[j] + C2[j]); scores may be NULL. The small joins — nearly all of a tree's — run
- * in two launches together, the few large ones as mpcgpu_align_alns does; every matrix and path is the single call's. */
+ * in two launches together, the few large ones as mpcgpu_align_alns does; every matrix and path is the single call's.
+ * Here, in mpcgpu_align_alns(_w), mpcgpu_build_post and mpcgpu_align_msas a row's position -> column map must rise strictly (as
+ * Sequence::GetPosToCol of an aligned row does); a map with two positions on one column or a step back is refused. */
 int mpcgpu_align_alns_batch(mpcgpu_ctx *ctx, uint32_t njoins, const uint32_t *n1, const uint32_t *n2, const uint32_t *C1,
                             const uint32_t *C2, const uint32_t *seqs, const uint32_t *pos2col, uint32_t path_stride,
                             char *paths, uint32_t *pathlens, float *scores);

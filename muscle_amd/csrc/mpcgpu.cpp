@@ -776,18 +776,20 @@ int mpcgpu_set_pair_order(mpcgpu_ctx *c, uint32_t nrects, const uint32_t *rects)
 	if (nrects && !rects) return fail(c, "mpcgpu_set_pair_order: no rectangles");
 	HIPCHK(c, hipSetDevice(c->device));
 	const u32 n = c->n;
-	c->have_shard = c->have_store = false;
-	c->partial = false;
-	if (c->order_rects.size() == 4 * (size_t)nrects && (nrects == 0 || !memcmp(c->order_rects.data(), rects, 16 * (size_t)nrects)))
+	if (c->order_rects.size() == 4 * (size_t)nrects && (nrects == 0 || !memcmp(c->order_rects.data(), rects, 16 * (size_t)nrects))) {
+		c->have_shard = c->have_store = false;
+		c->partial = false;
 		return 0; // the order the context already has (mpcgpu_set_seqs leaves InitPairs order)
-	c->order_rects.clear(); c->order_base.clear(); c->ext2pos.clear();
+	}
+	// the new order is built and checked aside: a rejected order leaves the context as it was (order, tables, shard and store)
+	std::vector<u32> px(c->npairs), py(c->npairs);
+	std::vector<u64> base(nrects);
 	u64 k = 0;
 	if (nrects == 0) { // back to MPCFlat::InitPairs order (mpcflat.cpp:145-155)
 		for (u32 i = 0; i < n; ++i)
-			for (u32 j = i + 1; j < n; ++j) { c->h_pair_x[k] = i; c->h_pair_y[k] = j; ++k; }
+			for (u32 j = i + 1; j < n; ++j) { px[k] = i; py[k] = j; ++k; }
 	} else {
 		std::vector<u8> seen(((u64)n * n + 7) / 8, 0); // every pair exactly once
-		std::vector<u64> base(nrects);
 		for (u32 r = 0; r < nrects; ++r) {
 			const u32 xa = rects[4 * r], xb = rects[4 * r + 1], ya = rects[4 * r + 2], yb = rects[4 * r + 3];
 			const bool tri = xa == ya && xb == yb;
@@ -799,24 +801,32 @@ int mpcgpu_set_pair_order(mpcgpu_ctx *c, uint32_t nrects, const uint32_t *rects)
 					const u64 bit = (u64)x * n + y;
 					if (k >= c->npairs || (seen[bit >> 3] >> (bit & 7)) & 1) return fail(c, "mpcgpu_set_pair_order: pair (%u,%u) is listed twice", x, y);
 					seen[bit >> 3] |= (u8)(1u << (bit & 7));
-					c->h_pair_x[k] = x; c->h_pair_y[k] = y; ++k;
+					px[k] = x; py[k] = y; ++k;
 				}
 		}
 		if (k != c->npairs) return fail(c, "mpcgpu_set_pair_order: the rectangles hold %llu of %llu pairs", (u64)k, (u64)c->npairs);
-		c->order_rects.assign(rects, rects + 4 * (size_t)nrects);
-		c->order_base = base;
+	}
+	std::vector<u32> e2p;
+	if (nrects) {
+		e2p.resize(c->npairs);
+		for (u64 q = 0; q < c->npairs; ++q) e2p[(u64)px[q] * n - ((u64)px[q] * (px[q] + 1)) / 2 + (py[q] - px[q] - 1)] = (u32)q;
+	}
+	// accepted: from here on the context takes the new order
+	c->have_shard = c->have_store = false;
+	c->partial = false;
+	c->order_rects.assign(rects, rects + 4 * (size_t)nrects);
+	c->order_base.swap(base);
+	c->ext2pos.swap(e2p);
+	c->h_pair_x.swap(px);
+	c->h_pair_y.swap(py);
+	if (nrects) {
 		std::vector<u32> dev(6 * (size_t)nrects);
 		for (u32 r = 0; r < nrects; ++r) {
 			for (u32 q = 0; q < 4; ++q) dev[6 * r + q] = rects[4 * r + q];
-			dev[6 * r + 4] = (u32)(base[r] & 0xffffffffull); dev[6 * r + 5] = (u32)(base[r] >> 32);
+			dev[6 * r + 4] = (u32)(c->order_base[r] & 0xffffffffull); dev[6 * r + 5] = (u32)(c->order_base[r] >> 32);
 		}
 		if (upload(c, c->d_rects, dev)) return 1;
 		HIPCHK(c, hipStreamSynchronize(c->stream)); // `dev` dies with this block
-		c->ext2pos.resize(c->npairs);
-		for (u64 q = 0; q < c->npairs; ++q) {
-			const u32 x = c->h_pair_x[q], y = c->h_pair_y[q];
-			c->ext2pos[(u64)x * n - ((u64)x * (x + 1)) / 2 + (y - x - 1)] = (u32)q;
-		}
 	}
 	if (upload(c, c->d_pair_x, c->h_pair_x) || upload(c, c->d_pair_y, c->h_pair_y)) return 1;
 	HIPCHK(c, hipStreamSynchronize(c->stream));

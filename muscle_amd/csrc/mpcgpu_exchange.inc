@@ -35,6 +35,21 @@ int mpcgpu_store_import_part(mpcgpu_ctx *c, uint32_t nshards, const uint64_t *k0
 	if (!c) return 1;
 	if (c->n == 0) return fail(c, "mpcgpu_store_import: call mpcgpu_set_seqs first");
 	if (own_k0 > own_k1 || own_k1 > c->npairs) return fail(c, "mpcgpu_store_import_part: bad own range [%llu,%llu)", (u64)own_k0, (u64)own_k1);
+	// where each shard lies in dev_all (offsets[s]; null: back to back in the order given); sorted by offset, no two may overlap. Checked
+	// before anything changes: a rejected call leaves the current store as it was
+	std::vector<u64> at(nshards, 0);
+	{
+		u64 run = 0;
+		for (u32 s = 0; s < nshards; ++s) { at[s] = offsets ? offsets[s] : run; run += bytes[s]; if (at[s] & 3) return fail(c, "mpcgpu_store_import: shard %u is not word-aligned", s); }
+		std::vector<u32> by_at(nshards);
+		for (u32 s = 0; s < nshards; ++s) by_at[s] = s;
+		std::sort(by_at.begin(), by_at.end(), [&](u32 a, u32 b) { return at[a] < at[b]; });
+		for (u32 q = 0; q + 1 < nshards; ++q) {
+			const u32 s = by_at[q], t = by_at[q + 1];
+			if (bytes[s] > at[t] - at[s])
+				return fail(c, "mpcgpu_store_import_part: shards %u and %u overlap ([%llu,+%llu) and [%llu,+%llu) bytes)", s, t, (u64)at[s], (u64)bytes[s], (u64)at[t], (u64)bytes[t]);
+		}
+	}
 	HIPCHK(c, hipSetDevice(c->device));
 	c->have_store = false;
 	c->tiles_k0 = c->tiles_k1 = ~0ull;
@@ -53,11 +68,6 @@ int mpcgpu_store_import_part(mpcgpu_ctx *c, uint32_t nshards, const uint64_t *k0
 	std::vector<u32> by_k(nshards);
 	for (u32 s = 0; s < nshards; ++s) by_k[s] = s;
 	std::sort(by_k.begin(), by_k.end(), [&](u32 a, u32 b) { return k0[a] != k0[b] ? k0[a] < k0[b] : k1[a] < k1[b]; });
-	std::vector<u64> at(nshards, 0);
-	{
-		u64 run = 0;
-		for (u32 s = 0; s < nshards; ++s) { at[s] = offsets ? offsets[s] : run; run += bytes[s]; if (at[s] & 3) return fail(c, "mpcgpu_store_import: shard %u is not word-aligned", s); }
-	}
 	c->all_nnz.assign(c->npairs, 0);
 	c->all_ea.assign(c->npairs, 0.0f);
 	c->h_pbase.assign(c->npairs + 1, 0);
@@ -204,7 +214,7 @@ int mpcgpu_values_export(mpcgpu_ctx *c, uint64_t first, uint64_t count, void *de
 {
 	if (!c) return 1;
 	if (!c->have_store) return fail(c, "mpcgpu_values_export: no store");
-	if (first + count > c->total_entries) return fail(c, "mpcgpu_values_export: range out of bounds");
+	if (count > c->total_entries || first > c->total_entries - count) return fail(c, "mpcgpu_values_export: range out of bounds");
 	HIPCHK(c, hipSetDevice(c->device));
 	if (count)
 		HIPCHK(c, hipMemcpyAsync(dev_dst, c->d_vnext.as<float>() + first, count * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -216,7 +226,7 @@ int mpcgpu_values_import(mpcgpu_ctx *c, uint64_t first, uint64_t count, const vo
 {
 	if (!c) return 1;
 	if (!c->have_store) return fail(c, "mpcgpu_values_import: no store");
-	if (first + count > c->total_entries) return fail(c, "mpcgpu_values_import: range out of bounds");
+	if (count > c->total_entries || first > c->total_entries - count) return fail(c, "mpcgpu_values_import: range out of bounds");
 	HIPCHK(c, hipSetDevice(c->device));
 	if (count)
 		HIPCHK(c, hipMemcpyAsync(c->d_vnext.as<float>() + first, dev_src, count * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -273,7 +283,7 @@ int mpcgpu_cons_commit_range(mpcgpu_ctx *c, uint64_t first, uint64_t count)
 {
 	if (!c) return 1;
 	if (!c->have_store) return fail(c, "mpcgpu_cons_commit: no store");
-	if (first + count > c->total_entries) return fail(c, "mpcgpu_cons_commit_range: range out of bounds");
+	if (count > c->total_entries || first > c->total_entries - count) return fail(c, "mpcgpu_cons_commit_range: range out of bounds");
 	HIPCHK(c, hipSetDevice(c->device));
 	if (count == 0) return 0;
 	StoreParams sp;

@@ -182,8 +182,10 @@ static int reduce_runs(mpcgpu_ctx *c, const RunBufs &rb, const u32 *keys_sorted,
 	return 0;
 }
 
-// BuildPost on the device store (+ CalcAlnFlat when path != NULL): the body of mpcgpu_align_alns_w and mpcgpu_build_post
-static int build_post_impl(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32_t n2, const uint32_t *seq2, uint32_t C1,
+// BuildPost on the device store (+ CalcAlnFlat when path != NULL): the body of mpcgpu_align_alns_w and mpcgpu_build_post (who: the
+// entry point, for the messages about the caller's maps). A row's position -> column map must rise strictly (Sequence::GetPosToCol of
+// an aligned row): two positions on one column would add twice into one cell of the matrix.
+static int build_post_impl(mpcgpu_ctx *c, const char *who, uint32_t n1, const uint32_t *seq1, uint32_t n2, const uint32_t *seq2, uint32_t C1,
 	uint32_t C2, const uint32_t *pos2col1, const uint32_t *pos2col2, const float *w1, const float *w2, char *path,
 	uint32_t *pathlen, float *score)
 {
@@ -240,7 +242,8 @@ static int build_post_impl(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uin
 				const u32 L = c->len[seq1[a]];
 				for (u32 pos = 0; pos < L; ++pos) {
 					const u32 col = pos2col1[at + pos];
-					if (col >= C1) return fail(c, "mpcgpu_align_alns: column map of MSA1 out of range");
+					if (col >= C1) return fail(c, "%s: column map of MSA1 out of range", who);
+					if (pos && col <= pos2col1[at + pos - 1]) return fail(c, "%s: column map of MSA1 row %u is not strictly increasing at position %u", who, a, pos);
 					c2p[(u64)a * C1 + col] = pos;
 				}
 				at += L;
@@ -248,7 +251,11 @@ static int build_post_impl(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uin
 			off2[0] = 0;
 			for (u32 b = 0; b < n2; ++b) off2[b + 1] = off2[b] + c->len[seq2[b]];
 			memcpy(maps2, pos2col2, 4 * len2);
-			for (u64 q = 0; q < len2; ++q) if (maps2[q] >= C2) return fail(c, "mpcgpu_align_alns: column map of MSA2 out of range");
+			for (u32 b = 0; b < n2; ++b)
+				for (u32 q = off2[b]; q < off2[b + 1]; ++q) {
+					if (maps2[q] >= C2) return fail(c, "%s: column map of MSA2 out of range", who);
+					if (q > off2[b] && maps2[q] <= maps2[q - 1]) return fail(c, "%s: column map of MSA2 row %u is not strictly increasing at position %u", who, b, q - off2[b]);
+				}
 			for (u32 a = 0; a < n1; ++a)
 				for (u32 b = 0; b < n2; ++b) if (seq1[a] == seq2[b]) return fail(c, "mpcgpu_align_alns: sequence %u is in both alignments", seq1[a]);
 			if (weighted) {
@@ -296,8 +303,13 @@ static int build_post_impl(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uin
 	for (u32 a = 0; a < n1 + n2; ++a) off[a + 1] = off[a] + c->len[seqs[a]];
 	memcpy(maps, pos2col1, len1 * 4);
 	memcpy(maps + len1, pos2col2, len2 * 4);
-	for (u64 q = 0; q < len1; ++q) if (maps[q] >= C1) return fail(c, "mpcgpu_align_alns: column map of MSA1 out of range");
-	for (u64 q = len1; q < len1 + len2; ++q) if (maps[q] >= C2) return fail(c, "mpcgpu_align_alns: column map of MSA2 out of range");
+	for (u32 a = 0; a < n1 + n2; ++a) {
+		const u32 C = a < n1 ? C1 : C2, side = a < n1 ? 1 : 2, row = a < n1 ? a : a - n1;
+		for (u64 q = off[a]; q < off[a + 1]; ++q) {
+			if (maps[q] >= C) return fail(c, "%s: column map of MSA%u out of range", who, side);
+			if (q > off[a] && maps[q] <= maps[q - 1]) return fail(c, "%s: column map of MSA%u row %u is not strictly increasing at position %u", who, side, row, (u32)(q - off[a]));
+		}
+	}
 	coff[0] = 0;
 	for (u32 a = 0; a < n1; ++a)
 		for (u32 b = 0; b < n2; ++b) {
@@ -375,7 +387,7 @@ int mpcgpu_align_alns_w(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32
 {
 	if (!c) return 1;
 	if (!path || !pathlen) return fail(c, "mpcgpu_align_alns: NULL argument");
-	return build_post_impl(c, n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, path, pathlen, score);
+	return build_post_impl(c, "mpcgpu_align_alns", n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, path, pathlen, score);
 }
 
 // A LIST of independent joins (the joins of one level of MPCFlat::ProgressiveAlign's guide tree, progalnflat.cpp:72-100: a join needs its
@@ -464,6 +476,7 @@ int mpcgpu_align_alns_batch(mpcgpu_ctx *c, uint32_t njoins, const uint32_t *n1, 
 				for (u32 pos = 0; pos < L; ++pos) {
 					const u32 col = mj[m + pos];
 					if (col >= C1[j]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA1 out of range (join %u)", j);
+					if (pos && col <= mj[m + pos - 1]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA1 row %u is not strictly increasing at position %u (join %u)", a, pos, j);
 					c2p[(u64)a * C1[j] + col] = pos;
 				}
 				m += L;
@@ -477,7 +490,12 @@ int mpcgpu_align_alns_batch(mpcgpu_ctx *c, uint32_t njoins, const uint32_t *n1, 
 			const u64 d_maps2 = at_in;
 			memcpy(maps2, mj + m, 4 * (size_t)off2[n2[j]]);
 			at_in += 4 * (u64)off2[n2[j]];
-			for (u32 e = 0; e < off2[n2[j]]; ++e) if (maps2[e] >= C2[j]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA2 out of range (join %u)", j);
+			for (u32 b = 0; b < n2[j]; ++b)
+				for (u32 e = off2[b]; e < off2[b + 1]; ++e) {
+					if (maps2[e] >= C2[j]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA2 out of range (join %u)", j);
+					if (e > off2[b] && maps2[e] <= maps2[e - 1])
+						return fail(c, "mpcgpu_align_alns_batch: column map of MSA2 row %u is not strictly increasing at position %u (join %u)", b, e - off2[b], j);
+				}
 			for (u32 a = 0; a < n1[j]; ++a)
 				for (u32 b = 0; b < n2[j]; ++b) if (sj[a] == sj[n1[j] + b]) return fail(c, "mpcgpu_align_alns_batch: sequence %u is in both alignments of join %u", sj[a], j);
 			BuildPostRowsParams &r = bp[q];
@@ -540,7 +558,7 @@ int mpcgpu_align_alns_batch(mpcgpu_ctx *c, uint32_t njoins, const uint32_t *n1, 
 		const u32 *sj = seqs + soff[j], *mj = pos2col + moff[j];
 		u64 len1 = 0;
 		for (u32 a = 0; a < n1[j]; ++a) len1 += c->len[sj[a]];
-		if (build_post_impl(c, n1[j], sj, n2[j], sj + n1[j], C1[j], C2[j], mj, mj + len1, nullptr, nullptr, paths + (u64)j * path_stride, &pathlens[j],
+		if (build_post_impl(c, "mpcgpu_align_alns_batch", n1[j], sj, n2[j], sj + n1[j], C1[j], C2[j], mj, mj + len1, nullptr, nullptr, paths + (u64)j * path_stride, &pathlens[j],
 			scores ? &scores[j] : nullptr)) return 1;
 	}
 	return 0;
@@ -551,7 +569,7 @@ int mpcgpu_build_post(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32_t
 {
 	if (!c) return 1;
 	if (!post) return fail(c, "mpcgpu_build_post: NULL argument");
-	if (build_post_impl(c, n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, nullptr, nullptr, nullptr)) return 1;
+	if (build_post_impl(c, "mpcgpu_build_post", n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, nullptr, nullptr, nullptr)) return 1;
 	return mpcgpu_get_last_post(c, C1, C2, post);
 }
 
@@ -588,8 +606,17 @@ int mpcgpu_align_msas(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, cons
 		coff[q + 1] = coff[q] + c->sh_nnz[q];
 		rbase[q + 1] = rbase[q] + rec_words(c->len[seq1[q]], c->len[seq2[q]], c->sh_nnz[q]);
 	}
-	for (u64 x = 0; x < off1[npairs]; ++x) if (pos2col1[x] >= C1) return fail(c, "mpcgpu_align_msas: column map of MSA1 out of range");
-	for (u64 x = 0; x < off2[npairs]; ++x) if (pos2col2[x] >= C2) return fail(c, "mpcgpu_align_msas: column map of MSA2 out of range");
+	// (a row's map must rise strictly, as in build_post_impl)
+	for (u32 q = 0; q < npairs; ++q) {
+		for (u64 x = off1[q]; x < off1[q + 1]; ++x) {
+			if (pos2col1[x] >= C1) return fail(c, "mpcgpu_align_msas: column map of MSA1 out of range");
+			if (x > off1[q] && pos2col1[x] <= pos2col1[x - 1]) return fail(c, "mpcgpu_align_msas: column map of MSA1 in pair %u is not strictly increasing at position %u", q, (u32)(x - off1[q]));
+		}
+		for (u64 x = off2[q]; x < off2[q + 1]; ++x) {
+			if (pos2col2[x] >= C2) return fail(c, "mpcgpu_align_msas: column map of MSA2 out of range");
+			if (x > off2[q] && pos2col2[x] <= pos2col2[x - 1]) return fail(c, "mpcgpu_align_msas: column map of MSA2 in pair %u is not strictly increasing at position %u", q, (u32)(x - off2[q]));
+		}
+	}
 	const u64 M = coff[npairs];
 	const u64 cells = (u64)C1 * C2;
 	if (cells > 0xffffffffull) return fail(c, "mpcgpu_align_msas: %llu cells exceed this build's cell index", (u64)cells);

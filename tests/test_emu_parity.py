@@ -697,3 +697,126 @@ def test_emu_relax_band_tiles_races(emu, mode):
         env.update({"EMU_DMA": "late"} if mode == "late" else {"EMU_SCHED": mode})
         got = _with_env(env, lambda: P.run_lib(seqs, lib_path=emu))
         P.assert_same(got, want, "band tiles, %s, %s" % (mode, form))
+
+
+# ---- custom pair orders (mpcgpu_set_pair_order: what the block partition of a multi-GPU run sets; tests/_pair_order.py) ----------
+PO_SEQS = dict(a=(9, 30, 12), b=(3, 60, 13))  # 12 ragged sequences: plan_partition cuts blocks at 2 and 3 ranks
+
+
+def _po_seqs():
+    (n1, l1, s1), (n2, l2, s2) = PO_SEQS["a"], PO_SEQS["b"]
+    return make_family(n1, l1, seed=s1) + make_family(n2, l2, seed=s2)
+
+
+def _po_orders(emu):
+    import _pair_order as PO
+    seqs = _po_seqs()
+    orders = PO.fixed_orders([len(s) for s in seqs], emu)
+    rng = np.random.default_rng(5)
+    for k in range(2):
+        orders["random %d" % k] = PO.random_order(len(seqs), rng)
+    return orders
+
+
+PO_ORDER_NAMES = ["one triangle", "reverse rows", "empty and one-sequence", "off-diagonal first", "plan_partition world 2",
+                  "plan_partition world 3", "random 0", "random 1"]
+
+
+def test_emu_pair_order_positions(emu):
+    """pair_position == the inverse of mpcflat.position_pairs for the fixed and 40 generated orders at 3..16 sequences"""
+    import _pair_order as PO
+    PO.check_positions_many(emu)
+
+
+def test_emu_pair_order_rectangle_check(emu):
+    """the rectangle check of mpcgpu_set_pair_order, in process (nothing has run on the context: no kernel reads the tables): every
+    invalid list is refused with its reason, and the order set before stays in force; empty rectangles are accepted"""
+    import _pair_order as PO
+    from muscle_amd._lib import MpcGpuError
+    seqs = make_family(7, 12, seed=3)
+    g = MpcGpu(0, emu)
+    g.set_hmm(*G.hmm_tables())
+    g.set_seqs(seqs)
+    a = np.array(PO.ORDER_A, np.uint32)
+    g.set_pair_order(a)
+    reasons = {"order_pair_twice": "pair \\(0,3\\) is listed twice", "order_pairs_missing": "hold 18 of 21 pairs",
+               "order_past_n": "rectangle 0 = \\[0,3\\) x \\[3,8\\)", "order_crosses_diagonal": "rectangle 0 = \\[0,4\\) x \\[3,7\\)",
+               "order_xa_after_xb": "rectangle 0 = \\[3,0\\)"}
+    for case, why in reasons.items():
+        with pytest.raises(MpcGpuError, match="mpcgpu_set_pair_order: .*" + why):
+            g.set_pair_order(np.array(PO.REJECT_ORDERS[case], np.uint32))
+        PO.check_positions(g, a)
+    with pytest.raises(MpcGpuError, match="mpcgpu_set_pair_order: no rectangles"):
+        g._ck(g.L.mpcgpu_set_pair_order(g.h, 3, None))
+    PO.check_positions(g, a)
+    with pytest.raises(MpcGpuError, match="pair \\(3,4\\) is listed twice"):  # a triangle over a rectangle
+        g.set_pair_order(np.array([[0, 3, 3, 7], [3, 7, 3, 7], [0, 3, 0, 3], [3, 5, 3, 5]], np.uint32))
+    with pytest.raises(MpcGpuError, match="rectangle 1"):  # an empty rectangle is still checked
+        g.set_pair_order(np.array([[0, 7, 0, 7], [5, 5, 2, 3]], np.uint32))
+    PO.check_positions(g, a)
+    empty = np.array([[0, 0, 0, 7], [0, 7, 0, 7], [7, 7, 7, 7], [2, 2, 4, 6], [3, 4, 3, 4]], np.uint32)
+    g.set_pair_order(empty)
+    PO.check_positions(g, empty)
+    g.close()
+
+
+@pytest.mark.parametrize("name", PO_ORDER_NAMES)
+def test_emu_pair_order_sharded_stage(emu, name):
+    """one order: stage A in 2-3 position ranges on contexts of their own, the shards imported from one buffer in shuffled order at
+    explicit offsets, the relax in two position halves — EA and every stage == the oracle"""
+    import _pair_order as PO
+    orders = _po_orders(emu)
+    assert set(PO_ORDER_NAMES) <= set(orders), sorted(orders)
+    PO.check_sharded_orders(emu, _po_seqs(), {name: orders[name]}, seed=PO_ORDER_NAMES.index(name))
+
+
+@pytest.mark.parametrize("env", [0, 1, 2, 3])
+def test_emu_pair_order_relax_kernels(emu, env):
+    """the sharded stage under a generated order with each relax kernel: band tiles, relax_var_kernel's two geometries, gather"""
+    import _pair_order as PO
+    seqs = make_family(8, 40, seed=21) + ["MKV", make_family(1, 70, seed=9)[0]]
+    rects = PO.random_order(len(seqs), np.random.default_rng(11 + env))
+    PO.check_sharded_orders(emu, seqs, {"random": rects}, seed=env, envs=[PO.RELAX_ENVS[env]])
+
+
+@pytest.mark.parametrize("which", ["random", "plan_partition world 3"])
+def test_emu_pair_order_partial_stores_and_values_exchange(emu, which):
+    """two contexts with partial stores of one custom order, the values crossing by values_export / values_import and
+    cons_commit_range (no group); store_complete; BuildPost (rows and sort) and AlignAlns against the restatement"""
+    import _pair_order as PO
+    seqs = _po_seqs()
+    rects = _po_orders(emu)["random 1" if which == "random" else which]
+    PO.check_partial_exchange(emu, seqs, rects, seed=3)
+
+
+def test_emu_pair_order_reorder_one_context(emu):
+    """order A, InitPairs, order B on one context, each run == the oracle; set_seqs with a new n resets the order"""
+    import _pair_order as PO
+    seqs = make_family(8, 36, seed=17)
+    rng = np.random.default_rng(2)
+    PO.check_reorder(emu, seqs, PO.random_order(8, rng), PO.fixed_orders([len(s) for s in seqs], emu)["reverse rows"])
+
+
+def test_emu_pair_order_mega(emu):
+    """structure-profile emissions under a shuffled order, whole and sharded"""
+    import _pair_order as PO
+    seqs = make_family(7, 30, seed=41)
+    PO.check_mega(emu, seqs, PO.random_order(7, np.random.default_rng(4)), seed=6)
+
+
+def _reject_cases():
+    import _pair_order as PO
+    return PO.REJECT_CASES
+
+
+@pytest.mark.parametrize("case", _reject_cases())
+def test_emu_rejected_call_changes_nothing(emu, case):
+    """an invalid set_pair_order / column map / shard layout / values range on a context that holds a finished run: refused by
+    name, positions and matrices as before, a valid run afterwards == the oracle. In a child process: an invalid call that is not
+    refused may crash it (the rectangles of a refused order used to be half written)."""
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONPATH=os.path.dirname(here) + os.pathsep + here)
+    r = subprocess.run([sys.executable, "-u", os.path.join(here, "_pair_order.py"), "reject", case, emu], env=env, cwd=here,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
+    assert r.returncode == 0 and ("OK " + case) in r.stdout, "exit %d\n%s" % (r.returncode, r.stdout[-3000:])

@@ -794,3 +794,115 @@ def test_align_pairs_vs_reference_golden():
 def test_fb_chains():
     """pairs that share their row sequence swept back to back (kernels_fbc.h) == one pair per sweep == the oracle"""
     P.check_fb_chains()
+
+
+# ---- custom pair orders (mpcgpu_set_pair_order: what the block partition of a multi-GPU run sets; tests/_pair_order.py) ----------
+# the emulator's cases, then 64..100 sequences of 100..300 residues and rows longer than 1024. No invalid argument goes to the
+# library here: the refused calls are checked on the emulator build (tests/test_emu_parity.py), where a miss cannot touch a device.
+_PO_ORACLE = {}
+
+
+def _po_family(n, length, seed):
+    key = (n, length, seed)
+    if key not in _PO_ORACLE:
+        seqs = make_family(n - 2, length, seed=seed) + make_family(2, length // 2, seed=seed + 1)  # ragged
+        _PO_ORACLE[key] = (seqs, P.run_oracle(seqs))
+    return _PO_ORACLE[key]
+
+
+PO_SMALL = ["one triangle", "reverse rows", "empty and one-sequence", "off-diagonal first", "plan_partition world 2",
+            "plan_partition world 3", "random 0", "random 1"]
+PO_LARGE = [(64, 150, 1), (80, 250, 2), (100, 300, 3)]
+
+
+def _po_small():
+    import _pair_order as PO
+    seqs = make_family(9, 30, seed=12) + make_family(3, 60, seed=13)
+    orders = PO.fixed_orders([len(s) for s in seqs], None)
+    rng = np.random.default_rng(5)
+    for k in range(2):
+        orders["random %d" % k] = PO.random_order(len(seqs), rng)
+    return seqs, orders
+
+
+def test_pair_order_positions():
+    """pair_position == the inverse of mpcflat.position_pairs for the fixed and 40 generated orders at 3..16 sequences"""
+    import _pair_order as PO
+    PO.check_positions_many(None)
+
+
+def test_pair_order_sharded_stage_small():
+    """every fixed order and two generated ones on 12 sequences: stage A in 2-3 position ranges on contexts of their own, the shards
+    imported from one device buffer in shuffled order at explicit offsets, the relax in two position halves == the oracle"""
+    import _pair_order as PO
+    seqs, orders = _po_small()
+    assert set(PO_SMALL) <= set(orders), sorted(orders)
+    PO.check_sharded_orders(None, seqs, orders, seed=1)
+
+
+@pytest.mark.parametrize("n,length,seed", PO_LARGE)
+def test_pair_order_sharded_stage_large(n, length, seed):
+    """a generated order, plan_partition's blocks at 3 and 8 ranks and reverse row order at 64..100 sequences"""
+    import _pair_order as PO
+    seqs, want = _po_family(n, length, seed)
+    fixed = PO.fixed_orders([len(s) for s in seqs], None, worlds=(3, 8))
+    orders = {"random": PO.random_order(n, np.random.default_rng(seed), max_groups=6), "reverse rows": fixed["reverse rows"],
+              "plan_partition world 3": fixed["plan_partition world 3"], "plan_partition world 8": fixed["plan_partition world 8"]}
+    PO.check_sharded_orders(None, seqs, orders, seed=seed, want=want)
+
+
+@pytest.mark.parametrize("env", [0, 1, 2, 3])
+def test_pair_order_relax_kernels(env):
+    """the sharded stage under a generated order with each relax kernel (band tiles, relax_var_kernel's two geometries, gather),
+    at 10 and at 64 sequences"""
+    import _pair_order as PO
+    seqs = make_family(8, 40, seed=21) + ["MKV", make_family(1, 70, seed=9)[0]]
+    rects = PO.random_order(len(seqs), np.random.default_rng(11 + env))
+    PO.check_sharded_orders(None, seqs, {"random": rects}, seed=env, envs=[PO.RELAX_ENVS[env]])
+    seqs, want = _po_family(*PO_LARGE[0])
+    rects = PO.random_order(len(seqs), np.random.default_rng(21 + env), max_groups=6)
+    PO.check_sharded_orders(None, seqs, {"random": rects}, seed=env, envs=[PO.RELAX_ENVS[env]], want=want)
+
+
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_pair_order_partial_stores_and_values_exchange(size):
+    """two contexts with partial stores of one custom order, the values crossing by values_export / values_import through device
+    buffers and cons_commit_range (no group); store_complete; BuildPost (rows and sort) and AlignAlns against the restatement"""
+    import _pair_order as PO
+    if size == "small":
+        seqs, orders = _po_small()
+        PO.check_partial_exchange(None, seqs, orders["plan_partition world 3"], seed=3)
+        PO.check_partial_exchange(None, seqs, orders["random 1"], seed=4)
+    else:
+        seqs, want = _po_family(*PO_LARGE[0])
+        rects = PO.random_order(len(seqs), np.random.default_rng(8), max_groups=6)
+        PO.check_partial_exchange(None, seqs, rects, seed=5, want=want, joins=1)
+
+
+def test_pair_order_reorder_one_context():
+    """order A, InitPairs, order B on one context, each run == the oracle; set_seqs with a new n resets the order"""
+    import _pair_order as PO
+    seqs = make_family(8, 36, seed=17)
+    PO.check_reorder(None, seqs, PO.random_order(8, np.random.default_rng(2)), PO.fixed_orders([len(s) for s in seqs], None)["reverse rows"])
+    seqs, want = _po_family(*PO_LARGE[0])
+    rng = np.random.default_rng(9)
+    PO.check_reorder(None, seqs, PO.random_order(len(seqs), rng, max_groups=6), PO.random_order(len(seqs), rng, max_groups=6), want=want)
+
+
+def test_pair_order_mega():
+    """structure-profile emissions under a shuffled order, whole and sharded"""
+    import _pair_order as PO
+    seqs = make_family(7, 30, seed=41)
+    PO.check_mega(None, seqs, PO.random_order(7, np.random.default_rng(4)), seed=6)
+
+
+def test_pair_order_long_rows():
+    """sequences longer than 1024 (the row-block stage A, fb_kernel<.., LONG>) under a shuffled order, whole and sharded"""
+    import _pair_order as PO
+    seqs = [make_family(1, 1400, seed=51)[0], make_family(1, 1030, seed=52)[0]] + make_family(4, 200, seed=53) + ["MKV"]
+    rects = PO.random_order(len(seqs), np.random.default_rng(6))
+    want = P.run_oracle(seqs)
+    g = PO.new_ctx(None, seqs, rects)
+    P.assert_same(PO.run_on(g), want, "long rows, custom order")
+    g.close()
+    PO.check_sharded_orders(None, seqs, {"random": rects}, seed=6, want=want)
