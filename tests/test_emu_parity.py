@@ -220,9 +220,113 @@ def test_emu_align_alns_long_runs(emu):
                         cnt[m1[a][col[k]], m2[b][i]] += 1
     assert cnt.max() > 512 and (cnt > 64).sum() > 10
     sc0, path0 = O.calc_aln(post)
+
+    def counts():
+        t = g.timers_get()
+        return tuple(t[k][1] for k in ("buildpost_gen", "buildpost_sort", "buildpost_reduce"))
+    g.timers_enable(True)
+    # 1024 pairs: by default the row form (one launch, no sort, no reduction)
+    g.timers_reset()
     path, sc = g.align_alns(grp1, grp2, m1, m2, C1, C2)
     assert path == path0 and P.bits(sc) == P.bits(sc0)
+    assert counts() == (1, 0, 0)
+    # the general path, whose in-order reduction is what the runs above test: the sort and the reduction ran
+    g.timers_reset()
+    path, sc = _with_env({"MPCGPU_BP": "sort"}, lambda: g.align_alns(grp1, grp2, m1, m2, C1, C2))
+    assert path == path0 and P.bits(sc) == P.bits(sc0)
+    assert counts() == (1, 1, 1)
+    assert np.array_equal(P.bits(g.last_post(C1, C2)), P.bits(post))
     g.close()
+
+
+# ---- the device joins' path table (tests/_joins.py), small: a change of the dispatcher fails here before GPU time is spent ------
+@pytest.fixture(scope="module")
+def joins_ctx(emu):
+    import _joins as J
+    ctx = J.Ctx(make_family(12, 30, seed=5) + J.HOMOPOLYMERS, emu)
+    yield ctx
+    ctx.close()
+
+
+# (name, MSA1 rows, MSA2 rows, Join arguments): the row form with 8 (C2 <= 512) and 16 (513..1024) columns per lane
+EMU_ROW_CASES = [("row8", [0, 3, 5], [1, 2, 6, 4], {}), ("row8 C2=512", [2, 7], [0, 9, 4], {"C2": 512}),
+                 ("row16 C2=513", [8, 1, 11], [10, 3], {"C2": 513}), ("row16 C2=1024", [5, 6], [4, 11, 0], {"C2": 1024}),
+                 ("row8 1 x n", [6], [0, 9, 11], {}), ("row8 n x 1", [1, 8, 3], [5], {})]
+
+
+@pytest.mark.parametrize("mode", [None, "sort"])
+@pytest.mark.parametrize("case", [c[0] for c in EMU_ROW_CASES])
+def test_emu_joins_row_form(joins_ctx, case, mode):
+    """every row-form case on its path, and again forced through the general path (MPCGPU_BP=sort): matrix, path and score bits
+    against the restatement, plain and weighted"""
+    name, grp1, grp2, kw = next(c for c in EMU_ROW_CASES if c[0] == case)
+    j = joins_ctx.join(grp1, grp2, np.random.default_rng(len(name)), **kw)
+    joins_ctx.check(j, "row" if mode is None else "general", mode=mode, what=name)
+
+
+def test_emu_joins_general_wide(joins_ctx):
+    """C2 = 1025: the general path without forcing"""
+    j = joins_ctx.join([0, 7, 2], [3, 9], np.random.default_rng(5), C2=1025)
+    joins_ctx.check(j, "general", what="C2 > 1024")
+
+
+def test_emu_joins_general_many_pairs(emu):
+    """46 x 46 = 2116 pairs: the general path without forcing (the row form takes at most 2048); the store without relax rounds"""
+    import _joins as J
+    ctx = J.Ctx(make_family(92, 8, seed=7), emu, iters=0)
+    try:
+        j = ctx.join(list(range(0, 92, 2)), list(range(1, 92, 2)), np.random.default_rng(6))
+        ctx.check(j, "general", what="pairs > 2048")
+    finally:
+        ctx.close()
+
+
+def test_emu_joins_row_list_overflow(joins_ctx):
+    """a chunk of 64 pairs whose output row lists more than 1024 entries: the row form reports it and the general path redoes the join"""
+    import _joins as J
+    j = joins_ctx.join(*J.overflow_groups(12), np.random.default_rng(8))
+    joins_ctx.check(j, "overflow", what="row list overflow")
+
+
+def test_emu_joins_batch_paths(joins_ctx):
+    """align_alns_batch: small joins in one chunk, joins that are not small (C2 + 1 > 512, C2 > 1024) in list order after them, a
+    chunk that overflows the row form's list (all its joins then take the single-join path) and a batch of one"""
+    import _joins as J
+    ctx = joins_ctx
+    rng = np.random.default_rng(12)
+    small = [ctx.join([0], [1], rng), ctx.join([2, 3], [4], rng), ctx.join([5, 6, 7], [8, 9], rng), ctx.join([11], [10, 0], rng),
+             ctx.join([4, 1], [3], rng, C1=638, C2=511)]
+    wide = ctx.join([9, 2], [6], rng, C2=600)
+    huge = ctx.join([3], [7, 10], rng, C2=1100)
+    joins = [small[0], wide, small[1], huge, small[2], small[3], small[4]]
+    chunks, single = ctx.check_batch(joins, "mixed")
+    assert chunks == [[0, 2, 4, 5, 6]] and single == [1, 3]
+    over = ctx.join(*J.overflow_groups(12), rng)
+    chunks, single = ctx.check_batch([small[0], over, wide, small[2]], "overflowed chunk")
+    assert chunks == [[0, 1, 3]] and sorted(single) == [0, 1, 2, 3]
+    chunks, single = ctx.check_batch([small[2]], "batch of one")
+    assert chunks == [] and single == [0]
+
+
+def test_emu_joins_alignment_kernels_traced(emu):
+    """one join ending in each alignment kernel (one wave, several waves with rows in registers, rows in LDS) and the overflowed
+    row form, proven by the MPCGPU_TRACE=1 lines of a child process"""
+    import _joins as J
+    J.check_aln_cases_traced(emu, "emu")
+
+
+def test_emu_align_msas_long_list():
+    """align_msas on 2500 pairs (repeated sequences, both index orders) over more than 512 columns: per-pair EA, matrix, path
+    and score against the oracle and the list-form restatement"""
+    import _joins as J
+    subprocess.check_call(["make", "-C", EMU_DIR], stdout=subprocess.DEVNULL)
+    rng = np.random.default_rng(21)
+    seqs = make_family(20, 12, seed=19)
+    grp1 = [int(x) for x in rng.integers(0, 10, 50) * 2]
+    grp2 = [int(x) for x in rng.integers(0, 10, 50) * 2 + 1]
+    pairs = [(a, b) for a in range(50) for b in range(50)]
+    C1, C2, npairs = J.check_align_msas(seqs, grp1, grp2, pairs, rng, EMU_LIB, extra=510, what="emu long list")
+    assert npairs > 2048 and min(C1, C2) > 512
 
 
 def test_emu_align_msas(emu):
