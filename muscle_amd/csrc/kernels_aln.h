@@ -266,12 +266,15 @@ __global__ void __launch_bounds__(256) dense_post_kernel(DensePostParams p)
 {
 	const u32 q = blockIdx.x;
 	const u32 LX = p.seq_len[p.pair_x[q]], LY = p.seq_len[p.pair_y[q]];
+	const u32 c = p.cand_cnt[q];
+	// an overflowed list (the short path of mpcgpu_align_pairs launches this before the host sees the flag) holds only its first
+	// capc entries; the count runs past its slot and the buffer. The host drops this matrix and redoes the pair.
+	if (c > p.capc) return;
 	float *M = p.out + p.out_off[q];
 	const u64 cells = (u64)LX * LY;
 	for (u64 e = threadIdx.x; e < cells; e += blockDim.x) M[e] = 0.0f;
 	__syncthreads();
 	const u32 kshift = LX >= p.long_min ? MPC_KEY_ROW_SHIFT_LONG : MPC_KEY_ROW_SHIFT;
-	const u32 c = p.cand_cnt[q];
 	const u64 *cand = p.cand + (u64)q * p.capc;
 	for (u32 e = threadIdx.x; e < c; e += blockDim.x) {
 		const u64 v = cand[e];

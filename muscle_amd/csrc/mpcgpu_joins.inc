@@ -736,6 +736,7 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 		fp.order = order + pos; fp.count = cnt;
 		fp.queue = c->d_queue.as<u32>() + H;
 		fp.fm_scratch = c->d_fm.as<float>(); fp.fm_stride = fm_stride;
+		if (trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs short list: fb H=%u pairs=%u\n", H, cnt); fflush(stderr); }
 		if (span_begin(c, 0, &sp)) return 1;
 		launch_fb_h((int)H, mega, fp, grid, block, fb_smem, c->stream);
 		HIPCHK(c, hipGetLastError());

@@ -275,7 +275,8 @@ def check_fb_chains(lib_path=None):
 
 def check_align_pairs_chunked(lib_path=None):
     """a list of 300 pairs (two stage-A chunks: 256 + 44) through mpcgpu_align_pairs + mpcgpu_get_list_sparse: every entry equals what the
-    same ordered pair gives as a list of one — paths, score / EA bits, sparse matrices"""
+    same ordered pair gives as a list of one — paths, score / EA bits, sparse matrices — and what the oracle gives (_align_pairs.ap_oracle)"""
+    import _align_pairs as A
     import _golden as G
     from muscle_amd._lib import MpcGpu
     from muscle_amd.synth import make_family
@@ -296,6 +297,9 @@ def check_align_pairs_chunked(lib_path=None):
         (path, sc, ea), (off, val) = one[(a, b)]
         assert res[q][0] == path and bits(res[q][1]) == bits(sc) and bits(res[q][2]) == bits(ea), q
         assert np.array_equal(sp[q][0], off) and np.array_equal(sp[q][1], val), (q, a, b)
+        w = A.oracle_pair(seqs, a, b)
+        assert res[q][0] == w["path"] and bits(res[q][1]) == bits(w["score"]) and bits(res[q][2]) == bits(w["ea"]), (q, a, b, "oracle")
+        assert np.array_equal(sp[q][0], w["off"]) and np.array_equal(sp[q][1], w["val"]), (q, a, b, "oracle")
     g.close()
 
 

@@ -712,6 +712,21 @@ def test_emu_align_pairs_list_longer_than_a_chunk(emu):
     P.check_align_pairs_chunked(emu)
 
 
+# ---- the device AlignPairFlat's path table (tests/_align_pairs.py), thin shapes and lowered limits ---------------------------
+def _ap_case_names():
+    import _align_pairs as A
+    return A.CASE_NAMES
+
+
+@pytest.mark.parametrize("name", _ap_case_names())
+def test_emu_align_pairs_case(emu, name):
+    """every call of the case against ap_oracle (path, score and EA bits, get_list_sparse), on its path by launch counters, and
+    again in a child process with MPCGPU_TRACE=1 by its trace lines"""
+    import _align_pairs as A
+    A.run_case(A.case("emu", name), emu)
+    A.check_case_traced("emu", name, emu)
+
+
 def test_emu_fb_chains(emu):
     """pairs that share their row sequence swept back to back (kernels_fbc.h) == one pair per sweep == the oracle"""
     P.check_fb_chains(emu)
