@@ -357,6 +357,9 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 			if (trace_on()) {
 				fprintf(stderr, "[mpcgpu] fb chains H=%u chains=%u grid=%u occ=%u longest axis=%u fm=%.1f MB\n", H, cnt, grid, occ, P.cvmax[H],
 					(double)grid * waves_per_block * fm_stride * 4 / 1048576.0);
+				u64 members = 0;
+				for (u32 k = 0; k < cnt; ++k) members += P.chain_cnt[cpos + k];
+				fprintf(stderr, "[mpcgpu] fb chain members H=%u pairs=%llu capc=%u batch=%llu\n", H, members, capc, B);
 				fflush(stderr);
 			}
 			FbChainParams cp;
@@ -475,6 +478,11 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 		if (overflow) {
 			if (capc >= LXmax * (u64)LYmax)
 				return fail(c, "mpcgpu_calc_posteriors: candidate overflow at full capacity (internal error)");
+			if (trace_on()) {
+				fprintf(stderr, "[mpcgpu] stage A overflow: batch at pair %llu (%llu pairs) redone, capc %u -> %llu, next batch %s\n", done, B, capc,
+					std::min<u64>((u64)capc * 2, (u64)LXmax * LYmax), nxt.valid ? "queued and dropped" : "not queued");
+				fflush(stderr);
+			}
 			capc = (u32)std::min<u64>((u64)capc * 2, (u64)LXmax * LYmax);
 			// redo this batch with a larger candidate capacity: what is queued behind it (the next batch's sweeps) is drained and dropped
 			HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -495,8 +503,14 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 		// (allocated with room to spare, asked for with less: the estimate moves by a fraction of a percent from batch to batch, and a
 		// buffer that is a hair too small is replaced — a device-to-device copy of gigabytes behind the next batch's sweeps, once per
 		// cold run: profiles/r13a_kernel_stats_1000x400.csv has 0.39 s of such copies in the first step of a process)
-		if (std::max<u64>(est, hdr + w * 4) > c->d_shard.cap)
+		if (std::max<u64>(est, hdr + w * 4) > c->d_shard.cap) {
+			const size_t cap0 = c->d_shard.cap;
 			HIPCHK(c, c->d_shard.ensure(std::max<u64>(hdr + (u64)(per * 1.15 * double(np) + 1024) * 4, hdr + w * 4), true, c->stream));
+			if (trace_on()) {
+				fprintf(stderr, "[mpcgpu] stage A shard: buffer %s at pair %llu, %zu -> %zu B, %llu record words kept\n", cap0 ? "replaced" : "allocated", done, cap0, c->d_shard.cap, words_done);
+				fflush(stderr);
+			}
+		}
 		if (upload(c, c->d_dstbase, dstbase) || upload(c, c->d_recwords, recw)) return 1;
 		if (span_begin(c, 1, &sp)) return 1;
 		MPC_LAUNCH(pack_kernel, (u32)std::min<u64>(B, (u64)cus * 8), 256, 0, c->stream, c->d_res.as<u32>(), res_stride,

@@ -116,7 +116,7 @@ def capc_of(lens, env):
 
 
 def regrowths(lens, cand, env):
-    """stage A's overflow retries on one batch (mpcgpu_stage_a.inc:475-483): the room doubles, up to LXmax * LYmax"""
+    """stage A's overflow retries on one batch (mpcgpu_stage_a.inc:478-491): the room doubles, up to LXmax * LYmax"""
     capc, n = capc_of(lens, env), 0
     full = max(a for a, _ in lens) * max(b for _, b in lens)
     while max(cand) > capc:
@@ -158,9 +158,10 @@ def chunks_of(n, env):
 
 
 # ---- the oracle -------------------------------------------------------------------------------------------------------------
-def ap_oracle(h, x, y, mega=None):
+def ap_oracle(h, x, y, mega=None, path=True):
     """AlignPairFlat_SparsePost (alignpairflat.cpp:3-27) on the oracle: mega = (O.make_mega(...), profile of x, profile of y) or None
-    -> dict(path, score, ea, off, val, cand: cells with Score >= MIN_SPARSE_SCORE, the candidate list the device keeps)"""
+    -> dict(path, score, ea, off, val, cand: cells with Score >= MIN_SPARSE_SCORE, the candidate list the device keeps).
+    path=False: the score alone (CalcAlnScoreFlat), as MPCFlat::CalcPosterior needs it (tests/_stage_a.py)"""
     if mega is None:
         F, B = O.fwd(h, x, y), O.bwd(h, x, y)
     else:
@@ -168,7 +169,8 @@ def ap_oracle(h, x, y, mega=None):
         F, B = O.fwd_mega(h, g, px, py), O.bwd_mega(h, g, px, py)
     LX, LY = len(x), len(y)
     Pd = O.post(F, B, LX, LY)
-    sc, path = O.calc_aln(Pd)
+    del F, B
+    sc, path = O.calc_aln(Pd) if path else (O.aln_score(Pd), None)
     off, val = O.sparse_from_post(Pd)
     return {"path": path, "score": np.float32(sc), "ea": np.float32(O.lib().orc_ea(sc, LX, LY)), "off": off, "val": val,
             "cand": int(np.count_nonzero(Pd))}

@@ -727,6 +727,20 @@ def test_emu_align_pairs_case(emu, name):
     A.check_case_traced("emu", name, emu)
 
 
+# ---- all-pairs stage A's path table (tests/_stage_a.py), thin shapes and lowered knobs ---------------------------------------
+def _sa_case_names():
+    import _stage_a as S
+    return S.CASE_NAMES
+
+
+@pytest.mark.parametrize("name", _sa_case_names())
+def test_emu_stage_a_case(emu, name):
+    """every run of the case against the oracle (EA bits, nnz, offsets, values; store and relax rounds), on its path by launch counters,
+    stage_a_info and the MPCGPU_TRACE=1 lines: the whole table runs once, in child processes side by side (_stage_a.emu_table)"""
+    import _stage_a as S
+    S.check_case_emu(name, emu)
+
+
 def test_emu_fb_chains(emu):
     """pairs that share their row sequence swept back to back (kernels_fbc.h) == one pair per sweep == the oracle"""
     P.check_fb_chains(emu)

@@ -77,6 +77,10 @@ def test_wildcards_and_lowercase():
 
 
 def test_ragged_and_extremes():
+    """lengths 1 .. 1024 in one run. Row sequences of 769 residues and more (900, 1000, 1024 here) take the row-block kernel
+    (mpcgpu_stage_a.inc: long_min = 769; 1024 was the last single-block length before that), the shorter ones (1, 1, 5 and 200
+    residues) the chain kernel (fb_chain_kernel<1> and <4>); the 333-residue sequence is last and only ever a column
+    sequence. tests/_stage_a.py pins the 768 / 769 and 1024 / 1025 boundaries with their trace lines."""
     long1024 = (make_family(1, 1100, seed=5)[0] * 2)[:1024]  # exactly the longest row sequence this build takes
     seqs = ["M", "W", "MKVLA", make_family(1, 900, seed=2)[0], make_family(1, 1000, seed=3)[0][:1024], long1024,
             "ACDEFGHIKLMNPQRSTVWY" * 10, make_family(1, 333, seed=4)[0]]
@@ -84,15 +88,19 @@ def test_ragged_and_extremes():
 
 
 def test_eight_rows_per_lane():
-    """449..512 residues: fb_kernel<8>, the instantiation held to 128 VGPRs by its launch bounds (a few spilled dwords)"""
+    """449..512 residues: eight rows per lane. With chains on (the default) these pairs run in fb_chain_kernel<8>, not in fb_kernel<8>
+    (the instantiation held to 128 VGPRs by its launch bounds, a few spilled dwords): that one runs under MPCGPU_FB_CHAIN=0 or with
+    structure profiles, which tests/_stage_a.py's bins_single / bins_mega cases do."""
     seqs = make_family(6, 480, seed=71) + [make_family(1, 512, seed=72)[0][:512], make_family(1, 449, seed=73)[0][:449]]
     P.assert_same(P.run_lib(seqs), P.run_oracle(seqs, threads=0), "8 rows per lane")
 
 
 def test_long_rows_row_blocks():
-    """X longer than 64*16 rows: the row-block kernel (fb_kernel<7, MEGA, LONG>: 448-row blocks chained through
-    the line buffers). 1024 is the last single-block length, 1025 the first with blocks; with 2049 columns the row-list
-    post kernel needs more than 64 KB of LDS; the relax of such records takes the gather fallback."""
+    """the row-block kernel (fb_kernel<7, MEGA, LONG>: 448-row blocks chained through the line buffers). Row sequences from 769
+    residues on take it (mpcgpu_stage_a.inc: long_min), so 1024 and 1025 both do here: 3 blocks each, no longer the boundary between
+    one block and several; 1500 has 4 blocks. The 2049-residue sequence is last, so it is only ever a column sequence:
+    with 2049 columns the row-list post kernel needs more than 64 KB of LDS;
+    the relax of such records takes the gather fallback."""
     seqs = [make_family(1, 1500, seed=41)[0][:1500], (make_family(1, 1100, seed=42)[0] * 2)[:1025],
             (make_family(1, 1100, seed=43)[0] * 2)[:1024], make_family(1, 333, seed=44)[0],
             (make_family(1, 2300, seed=45)[0] * 2)[:2049]]
