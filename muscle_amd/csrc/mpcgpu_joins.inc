@@ -73,45 +73,22 @@ int mpcgpu_post_scores(mpcgpu_ctx *c, uint32_t LX, uint32_t LY, uint32_t ncand, 
 	const std::vector<u32> lens = {LX, LY}, zero = {0}, one = {1}, cnt = {ncand};
 	DevBuf d_len, d_x, d_y, d_cnt, d_cand, d_res, d_out, d_sort, d_srow;
 	auto free_all = [&]() { for (DevBuf *b : {&d_len, &d_x, &d_y, &d_cnt, &d_cand, &d_res, &d_out, &d_sort, &d_srow}) b->release(); };
-	const u64 res_stride = (u64)LX + LY + 4 * (u64)capc;
+	StageAGeom g; g.LXmax = LX; g.LYmax = LY; g.long_min = long_min; g.capc = capc; // of the one pair
+	const u64 res_stride = g.res_stride();
 	int rc = 0;
 	do {
 		if (upload(c, d_len, lens) || upload(c, d_x, zero) || upload(c, d_y, one) || upload(c, d_cnt, cnt) || upload(c, d_cand, cand)) { rc = 1; break; }
 		if (d_res.ensure(res_stride * 4) != hipSuccess || d_out.ensure(16) != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: out of device memory"); break; }
+		const PostIO io = {d_x.as<u32>(), d_y.as<u32>(), d_len.as<u32>(), d_cand.as<u64>(), d_cnt.as<u32>(), d_res.as<u32>(), d_out.as<u32>(), d_out.as<float>() + 1, d_out.as<u32>() + 2, 1};
 		if (kernel == 0) {
-			PostRowsParams pr;
-			pr.pair_x = d_x.as<u32>(); pr.pair_y = d_y.as<u32>(); pr.seq_len = d_len.as<u32>();
-			pr.cand = d_cand.as<u64>(); pr.capc = capc; pr.cand_cnt = d_cnt.as<u32>();
-			pr.use_fma = c->use_fma;
-			pr.lx_cap = LX + 2; pr.ly_cap = LY + 2;
-			pr.sort_cap = std::min<u32>(capc, 1024u); pr.sort_stride = capc;
-			pr.batch = std::min<u32>(std::max<u32>(batch, 1u), 64u);
-			const size_t fixed_lds = ((((size_t)pr.lx_cap + 2 * (size_t)pr.ly_cap) * 4 + 7) & ~(size_t)7);
-			if (fixed_lds + 16 > 150 * 1024) { rc = fail(c, "mpcgpu_post_scores: %u x %u does not fit the row-list kernel", LX, LY); break; }
-			if (fixed_lds + (size_t)pr.sort_cap * 8 > 150 * 1024) pr.sort_cap = (u32)((150 * 1024 - fixed_lds) / 8);
-			const size_t smem = fixed_lds + (size_t)pr.sort_cap * 8;
-			if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)post_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: LDS"); break; }
+			if (!post_rows_fits(LX, LY, 1)) { rc = fail(c, "mpcgpu_post_scores: %u x %u does not fit the row-list kernel", LX, LY); break; }
 			if (d_sort.ensure((u64)capc * 8 + 8) != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: out of device memory"); break; }
-			pr.sort_scratch = d_sort.as<u64>();
-			pr.res = d_res.as<u32>(); pr.res_stride = res_stride;
-			pr.nnz = d_out.as<u32>(); pr.ea = d_out.as<float>() + 1; pr.flags = d_out.as<u32>() + 2;
-			pr.count = 1; pr.long_min = long_min;
-			MPC_LAUNCH(post_rows_kernel, 1, 64, smem, c->stream, pr);
+			if (launch_post_rows(c, g, io, 1024, batch, 1, d_sort, false)) { rc = 1; break; }
 		} else {
 			PostParams pp;
-			pp.pair_x = d_x.as<u32>(); pp.pair_y = d_y.as<u32>(); pp.seq_len = d_len.as<u32>();
-			pp.cand = d_cand.as<u64>(); pp.capc = capc; pp.cand_cnt = d_cnt.as<u32>();
-			pp.use_fma = c->use_fma;
-			pp.sort_cap = std::min<u32>(next_pow2(std::max<u32>(capc, 2)), 1024u);
-			pp.srow_cap = std::min<u32>(LY + 1, 2048u);
-			pp.sort_stride = next_pow2(std::max<u32>(capc, 2));
-			pp.srow_stride = 2 * ((u64)LY + 1);
+			const size_t psmem = fill_post(c, g, io, 1024, pp);
 			if (d_sort.ensure(pp.sort_stride * 8) != hipSuccess || d_srow.ensure(pp.srow_stride * 4) != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: out of device memory"); break; }
 			pp.sort_scratch = d_sort.as<u64>(); pp.srow_scratch = d_srow.as<float>();
-			pp.res = d_res.as<u32>(); pp.res_stride = res_stride;
-			pp.nnz = d_out.as<u32>(); pp.ea = d_out.as<float>() + 1; pp.flags = d_out.as<u32>() + 2;
-			pp.count = 1; pp.long_min = long_min;
-			const size_t psmem = (size_t)pp.sort_cap * 8 + (size_t)pp.srow_cap * 2 * 4;
 			MPC_LAUNCH(post_kernel, 1, 64, psmem, c->stream, pp);
 		}
 		if (hipGetLastError() != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: launch failed"); break; }
@@ -390,6 +367,21 @@ int mpcgpu_align_alns_w(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32
 	return build_post_impl(c, "mpcgpu_align_alns", n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, path, pathlen, score);
 }
 
+// calc_aln_wave_batch_kernel, a workgroup of one wave per AlnParams record; lds_rows: the longest LX + 1 among them
+static int launch_aln_wave_batch(mpcgpu_ctx *c, const AlnParams *ap, u32 n, u32 lds_rows)
+{
+	const size_t smem = (size_t)lds_rows * MPC_ALNW_ROWBYTES + 16;
+	if (smem > c->aln_smem_set[3]) {
+		(void)hipFuncSetAttribute((const void *)calc_aln_wave_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+		c->aln_smem_set[3] = smem;
+	}
+	TimedSpan ts;
+	if (span_begin(c, 8, &ts)) return 1;
+	MPC_LAUNCH(calc_aln_wave_batch_kernel, n, 64, smem, c->stream, ap);
+	HIPCHK(c, hipGetLastError());
+	return span_end(c, &ts);
+}
+
 // A LIST of independent joins (the joins of one level of MPCFlat::ProgressiveAlign's guide tree, progalnflat.cpp:72-100: a join needs its
 // two children, joins of different subtrees nothing of each other). The small ones — the row form of BuildPost and the one-wave
 // alignment: what nearly all joins of a tree are — run TOGETHER: one launch builds every matrix (a workgroup per output row of a join),
@@ -522,15 +514,7 @@ int mpcgpu_align_alns_batch(mpcgpu_ctx *c, uint32_t njoins, const uint32_t *n1, 
 		if (any16) MPC_LAUNCH(build_post_rows_batch_kernel<16>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)nrows);
 		HIPCHK(c, hipGetLastError());
 		if (span_end(c, &ts)) return 1;
-		const size_t smem = (size_t)lds_rows * MPC_ALNW_ROWBYTES + 16;
-		if (smem > c->aln_smem_set[3]) {
-			(void)hipFuncSetAttribute((const void *)calc_aln_wave_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-			c->aln_smem_set[3] = smem;
-		}
-		if (span_begin(c, 8, &ts)) return 1;
-		MPC_LAUNCH(calc_aln_wave_batch_kernel, nb, 64, smem, c->stream, (const AlnParams *)(din + o_ap));
-		HIPCHK(c, hipGetLastError());
-		if (span_end(c, &ts)) return 1;
+		if (launch_aln_wave_batch(c, (const AlnParams *)(din + o_ap), nb, lds_rows)) return 1;
 		u32 err = 0;
 		HIPCHK(c, hipMemcpyAsync(&err, din + o_err, 4, hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -665,136 +649,25 @@ int mpcgpu_align_msas(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, cons
 	return run_calc_aln(c, c->d_aln_post.as<float>(), C1, C2, path, pathlen, score); // syncs before the vectors above die
 }
 
-// mpcgpu_align_pairs for a SHORT list (what UClust::Search and single AlignPairFlat calls send: 1..8 pairs): the kernels of the
-// general path, driven with one wait. Everything the kernels read from the host (pair list, launch order, alignment parameters)
-// and everything the host reads back (candidate-overflow flags, path records) lives in ONE page-locked record that the device
-// addresses directly; nothing is packed into a shard (mpcgpu_get_list_sparse re-runs the general stage when somebody asks).
-// 0 = done, 1 = error, 2 = not applicable (the caller takes the general path).
-static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py, u32 path_stride, char *paths, u32 *pathlens,
-	float *scores, float *ea)
+// The one-wave alignments of n pairs (sx[q], sy[q]), their dense matrices at off[q] of c->d_aln_post, in ONE launch: parameters in (ap) and a
+// record {length, score, path} per pair out (res, aln_rec_stride() apart) through page-locked memory that the device addresses; one wait.
+// ovf: candidate-overflow flags that the same wait brings back (the short list; else NULL): one of them set = 2, nothing handed out.
+static u64 aln_rec_stride(u32 Lsum_max) { return ((u64)8 + Lsum_max + 7) & ~7ull; }
+static int align_wave_batch(mpcgpu_ctx *c, u32 n, const u32 *sx, const u32 *sy, const u64 *off, u32 LXmax, u32 Lsum_max, AlnParams *ap, char *res, const u32 *ovf, u32 path_stride, char *paths, u32 *pathlens, float *scores, float *ea)
 {
-	const u32 long_min = (u32)std::min(std::max(env_int("MPCGPU_FB_LONG_MIN", 64 * 12 + 1), 2), 64 * MPC_HMAX + 1);
-	u32 LXmax = 0, LYmax = 0, Lsum_max = 0;
-	for (u32 q = 0; q < np; ++q) {
-		const u32 LX = c->len[px[q]], LY = c->len[py[q]];
-		if (LX >= long_min) return 2; // row-block pairs: general path
-		if ((u64)LY + 1 > MPC_ALNW_MAXW || (size_t)(LX + 1) * MPC_ALNW_ROWBYTES + 16 > 160u * 1024u) return 2; // not a one-wave alignment
-		LXmax = std::max(LXmax, LX); LYmax = std::max(LYmax, LY); Lsum_max = std::max(Lsum_max, LX + LY);
-	}
-	if (((size_t)LXmax + 2 + 2 * ((size_t)LYmax + 2)) * 4 + 8 + 8 * 1024 > 150 * 1024) return 2;
-	const u32 Lmax = std::max(LXmax, LYmax);
-	const u32 capc = std::max((u32)std::max(env_int("MPCGPU_CAND_PER_ROW", 12), 1) * Lmax, 1024u);
-	const bool mega = c->have_mega;
-	c->have_shard = c->have_store = false;
-	c->shard_is_list = true;
-	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np);
-	c->list_q0 = 0; c->ap_x.clear(); c->ap_y.clear();
-	c->sh_k0 = 0; c->sh_k1 = np;
-	// ---- the page-locked record
-	std::vector<u64> off(np + 1, 0);
-	for (u32 q = 0; q < np; ++q) off[q + 1] = off[q] + (u64)c->len[px[q]] * c->len[py[q]];
-	const u64 rstride = ((u64)8 + Lsum_max + 7) & ~7ull;
-	const u64 o_bx = 0, o_by = o_bx + 4 * (u64)np, o_order = o_by + 4 * (u64)np, o_off = (o_order + 4 * (u64)np + 7) & ~7ull,
-		o_par = o_off + 8 * ((u64)np + 1), o_flags = o_par + (u64)np * sizeof(AlnParams), o_nnz = o_flags + 4 * (u64)np,
-		o_ea = o_nnz + 4 * (u64)np, o_res = (o_ea + 4 * (u64)np + 7) & ~7ull, bytes = o_res + (u64)np * rstride;
-	HIPCHK(c, c->h_ap.ensure(bytes));
-	char *h = c->h_ap.as<char>();
-	u32 *bx = (u32 *)(h + o_bx), *by = (u32 *)(h + o_by), *order = (u32 *)(h + o_order);
-	memcpy(bx, px, 4 * (size_t)np);
-	memcpy(by, py, 4 * (size_t)np);
-	memcpy(h + o_off, off.data(), 8 * ((size_t)np + 1));
-	u32 hcount[MPC_HMAX + 1] = {0};
-	{
-		std::vector<u32> keys(np);
-		for (u32 q = 0; q < np; ++q) { const u32 H = (c->len[px[q]] + 63) / 64; hcount[H]++; keys[q] = (H << 16) | q; }
-		std::sort(keys.begin(), keys.end());
-		for (u32 q = 0; q < np; ++q) order[q] = keys[q] & 0xffffu;
-	}
-	// ---- scratch
-	const u64 res_stride = (u64)LXmax + LYmax + 4 * (u64)capc;
-	const int waves_per_block = 4, block = 64 * waves_per_block;
-	const size_t fb_smem = (mega ? (size_t)c->mg_tab_floats : (size_t)c->A * c->A + c->A) * sizeof(float);
-	HIPCHK(c, c->d_cand.ensure((u64)np * capc * 8));
-	HIPCHK(c, c->d_cand_cnt.ensure((u64)np * 4));
-	HIPCHK(c, c->d_total.ensure((u64)np * 4));
-	HIPCHK(c, c->d_res.ensure((u64)np * res_stride * 4));
-	HIPCHK(c, c->d_queue.ensure(4 * (MPC_HMAX + 2)));
-	HIPCHK(c, c->d_aln_post.ensure_grow(off[np] * 4));
-	HIPCHK(c, c->d_aln_rev.ensure_grow((u64)np * Lsum_max + 16));
-	HIPCHK(c, hipMemsetAsync(c->d_queue.p, 0, 4 * (MPC_HMAX + 2), c->stream));
-	// ---- forward / backward, one launch per rows-per-lane bin
-	FbParams fp;
-	fill_fb_params(c, fp, bx, by, capc, mega);
-	TimedSpan sp;
-	u32 pos = 0;
-	for (u32 H = 1; H <= MPC_HMAX; ++H) {
-		if (!hcount[H]) continue;
-		const u32 cnt = hcount[H];
-		const u32 grid = (cnt + waves_per_block - 1) / waves_per_block;
-		const u64 fm_stride = (u64)(LYmax + 64) * H * 64;
-		HIPCHK(c, c->d_fm.ensure((u64)grid * waves_per_block * fm_stride * 4));
-		fp.order = order + pos; fp.count = cnt;
-		fp.queue = c->d_queue.as<u32>() + H;
-		fp.fm_scratch = c->d_fm.as<float>(); fp.fm_stride = fm_stride;
-		if (trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs short list: fb H=%u pairs=%u\n", H, cnt); fflush(stderr); }
-		if (span_begin(c, 0, &sp)) return 1;
-		launch_fb_h((int)H, mega, fp, grid, block, fb_smem, c->stream);
-		HIPCHK(c, hipGetLastError());
-		if (span_end(c, &sp)) return 1;
-		pos += cnt;
-	}
-	// ---- probabilities, EA, sparsify (the candidate lists keep the probabilities)
-	PostRowsParams pr;
-	pr.pair_x = bx; pr.pair_y = by; pr.seq_len = c->d_seq_len.as<u32>();
-	pr.cand = c->d_cand.as<u64>(); pr.capc = capc; pr.cand_cnt = c->d_cand_cnt.as<u32>();
-	pr.use_fma = c->use_fma;
-	pr.lx_cap = LXmax + 2; pr.ly_cap = LYmax + 2;
-	pr.sort_cap = std::min<u32>(capc, 1024u); pr.sort_stride = capc;
-	pr.batch = 64;
-	const size_t fixed_lds = ((((size_t)pr.lx_cap + 2 * (size_t)pr.ly_cap) * 4 + 7) & ~(size_t)7);
-	const size_t smem = fixed_lds + (size_t)pr.sort_cap * 8;
-	if (smem > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void *)post_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-	HIPCHK(c, c->d_sort_scratch.ensure(capc > pr.sort_cap ? (u64)np * pr.sort_stride * 8 : 8));
-	pr.sort_scratch = c->d_sort_scratch.as<u64>();
-	pr.res = c->d_res.as<u32>(); pr.res_stride = res_stride;
-	pr.nnz = (u32 *)(h + o_nnz); pr.ea = (float *)(h + o_ea); pr.flags = (u32 *)(h + o_flags);
-	pr.count = np; pr.long_min = long_min;
-	if (span_begin(c, 1, &sp)) return 1;
-	MPC_LAUNCH(post_rows_kernel, np, 64, smem, c->stream, pr);
-	HIPCHK(c, hipGetLastError());
-	if (span_end(c, &sp)) return 1;
-	// ---- dense thresholded posteriors, alignments
-	DensePostParams dp;
-	dp.pair_x = bx; dp.pair_y = by; dp.seq_len = c->d_seq_len.as<u32>();
-	dp.cand = c->d_cand.as<u64>(); dp.capc = capc; dp.cand_cnt = c->d_cand_cnt.as<u32>(); dp.long_min = long_min;
-	dp.out_off = (const u64 *)(h + o_off); dp.out = c->d_aln_post.as<float>();
-	MPC_LAUNCH(dense_post_kernel, np, 256, 0, c->stream, dp);
-	HIPCHK(c, hipGetLastError());
-	c->last_post_cells = 0;
-	AlnParams *ap = (AlnParams *)(h + o_par);
-	for (u32 q = 0; q < np; ++q) {
-		char *r = h + o_res + (u64)q * rstride;
+	const u64 rstride = aln_rec_stride(Lsum_max);
+	for (u32 q = 0; q < n; ++q) {
+		char *r = res + (u64)q * rstride;
 		ap[q].post = c->d_aln_post.as<float>() + off[q];
-		ap[q].LX = c->len[px[q]]; ap[q].LY = c->len[py[q]];
+		ap[q].LX = c->len[sx[q]]; ap[q].LY = c->len[sy[q]];
 		ap[q].tb = nullptr; ap[q].rev = c->d_aln_rev.as<char>() + (u64)q * Lsum_max;
 		ap[q].pathlen = (u32 *)r; ap[q].score = (float *)(r + 4); ap[q].path = r + 8;
 	}
-	const size_t asmem = (size_t)(LXmax + 1) * MPC_ALNW_ROWBYTES + 16;
-	if (asmem > c->aln_smem_set[3]) {
-		(void)hipFuncSetAttribute((const void *)calc_aln_wave_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)asmem);
-		c->aln_smem_set[3] = asmem;
-	}
-	if (span_begin(c, 8, &sp)) return 1;
-	MPC_LAUNCH(calc_aln_wave_batch_kernel, np, 64, asmem, c->stream, (const AlnParams *)ap);
-	HIPCHK(c, hipGetLastError());
-	if (span_end(c, &sp)) return 1;
+	if (launch_aln_wave_batch(c, ap, n, LXmax + 1)) return 1;
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // the one wait
-	for (u32 q = 0; q < np; ++q)
-		if (((const u32 *)(h + o_flags))[q] & 1u) return 2; // a candidate list overflowed: the general path grows it and retries
-	c->sh_nnz.assign((const u32 *)(h + o_nnz), (const u32 *)(h + o_nnz) + np);
-	c->sh_ea.assign((const float *)(h + o_ea), (const float *)(h + o_ea) + np);
-	for (u32 q = 0; q < np; ++q) {
-		const char *r = h + o_res + (u64)q * rstride;
+	for (u32 q = 0; ovf && q < n; ++q) if (ovf[q] & 1u) return 2;
+	for (u32 q = 0; q < n; ++q) {
+		const char *r = res + (u64)q * rstride;
 		u32 n_path;
 		memcpy(&n_path, r, 4);
 		if (n_path > ap[q].LX + ap[q].LY) return fail(c, "mpcgpu_align_pairs: path length %u out of range (internal error)", n_path);
@@ -808,6 +681,72 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 	return 0;
 }
 
+// mpcgpu_align_pairs for a SHORT list (what UClust::Search and single AlignPairFlat calls send: 1..8 pairs): the kernels of the
+// general path, driven with one wait. Everything the kernels read from the host (pair list, launch order, alignment parameters)
+// and everything the host reads back (candidate-overflow flags, path records) lives in ONE page-locked record that the device
+// addresses directly; nothing is packed into a shard (mpcgpu_get_list_sparse re-runs the general stage when somebody asks).
+// 0 = done, 1 = error, 2 = not applicable (the caller takes the general path).
+static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py, u32 path_stride, char *paths, u32 *pathlens,
+	float *scores, float *ea)
+{
+	const StageAGeom g = stage_a_geom(c, np, px, py);
+	if (g.LXlong) return 2; // row-block pairs: general path
+	u32 Lsum_max = 0;
+	for (u32 q = 0; q < np; ++q) {
+		const u32 LX = c->len[px[q]], LY = c->len[py[q]];
+		if ((u64)LY + 1 > MPC_ALNW_MAXW || (size_t)(LX + 1) * MPC_ALNW_ROWBYTES + 16 > 160u * 1024u) return 2; // not a one-wave alignment
+		Lsum_max = std::max(Lsum_max, LX + LY);
+	}
+	if (!post_rows_fits(g.LXmax, g.LYmax, 1024)) return 2;
+	c->have_shard = c->have_store = false;
+	c->shard_is_list = true;
+	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np);
+	c->list_q0 = 0; c->ap_x.clear(); c->ap_y.clear();
+	c->sh_k0 = 0; c->sh_k1 = np;
+	// ---- the page-locked record
+	std::vector<u64> off(np + 1, 0);
+	for (u32 q = 0; q < np; ++q) off[q + 1] = off[q] + (u64)c->len[px[q]] * c->len[py[q]];
+	const u64 o_bx = 0, o_by = o_bx + 4 * (u64)np, o_order = o_by + 4 * (u64)np, o_off = (o_order + 4 * (u64)np + 7) & ~7ull,
+		o_par = o_off + 8 * ((u64)np + 1), o_flags = o_par + (u64)np * sizeof(AlnParams), o_nnz = o_flags + 4 * (u64)np,
+		o_ea = o_nnz + 4 * (u64)np, o_res = (o_ea + 4 * (u64)np + 7) & ~7ull, bytes = o_res + (u64)np * aln_rec_stride(Lsum_max);
+	HIPCHK(c, c->h_ap.ensure(bytes));
+	char *h = c->h_ap.as<char>();
+	u32 *bx = (u32 *)(h + o_bx), *by = (u32 *)(h + o_by), *order = (u32 *)(h + o_order);
+	memcpy(bx, px, 4 * (size_t)np);
+	memcpy(by, py, 4 * (size_t)np);
+	memcpy(h + o_off, off.data(), 8 * ((size_t)np + 1));
+	u32 hcount[MPC_HMAX + 1] = {0};
+	std::vector<u32> keys(np);
+	for (u32 q = 0; q < np; ++q) { const u32 H = (c->len[px[q]] + 63) / 64; hcount[H]++; keys[q] = (H << 16) | q; }
+	std::sort(keys.begin(), keys.end());
+	for (u32 q = 0; q < np; ++q) order[q] = keys[q] & 0xffffu;
+	// ---- scratch
+	if (ensure_pair_scratch(c, g, np)) return 1;
+	HIPCHK(c, c->d_aln_post.ensure_grow(off[np] * 4));
+	HIPCHK(c, c->d_aln_rev.ensure_grow((u64)np * Lsum_max + 16));
+	// ---- forward / backward, one launch per rows-per-lane bin
+	FbParams fp;
+	fill_fb_params(c, fp, bx, by, g.capc, g.mega);
+	if (launch_fb_bins(c, g, fp, order, hcount, 0)) return 1;
+	// ---- probabilities, EA, sparsify (the candidate lists keep the probabilities): a workgroup per pair, the knobs of the general stage ignored
+	const PostIO io = {bx, by, c->d_seq_len.as<u32>(), c->d_cand.as<u64>(), c->d_cand_cnt.as<u32>(), c->d_res.as<u32>(), (u32 *)(h + o_nnz), (float *)(h + o_ea), (u32 *)(h + o_flags), np};
+	if (launch_post_rows(c, g, io, 1024, 64, np, c->d_sort_scratch, true)) return 1;
+	// ---- dense thresholded posteriors, alignments
+	DensePostParams dp;
+	dp.pair_x = bx; dp.pair_y = by; dp.seq_len = c->d_seq_len.as<u32>();
+	dp.cand = c->d_cand.as<u64>(); dp.capc = g.capc; dp.cand_cnt = c->d_cand_cnt.as<u32>(); dp.long_min = g.long_min;
+	dp.out_off = (const u64 *)(h + o_off); dp.out = c->d_aln_post.as<float>();
+	MPC_LAUNCH(dense_post_kernel, np, 256, 0, c->stream, dp);
+	HIPCHK(c, hipGetLastError());
+	c->last_post_cells = 0;
+	const int rc = align_wave_batch(c, np, px, py, off.data(), g.LXmax, Lsum_max, (AlnParams *)(h + o_par), h + o_res, (const u32 *)(h + o_flags), path_stride, paths, pathlens, scores, ea);
+	if (rc) return rc; // (2: a candidate list overflowed: the general path grows it and retries)
+	c->sh_nnz.assign((const u32 *)(h + o_nnz), (const u32 *)(h + o_nnz) + np);
+	c->sh_ea.assign((const float *)(h + o_ea), (const float *)(h + o_ea) + np);
+	return 0;
+}
+
+struct KeepList { mpcgpu_ctx *c; ~KeepList() { c->ap_keep = false; } }; // c->ap_keep (set by the owner) is dropped on every way out
 // AlignPairFlat (alignpairflat.cpp:3-27) for a list of pairs: CalcPost (fwd + bwd + CalcPostFlat, calcpost.cpp:4-36) -> CalcAlnFlat on
 // the DENSE thresholded posterior -> path; EA = Score / min(L1, L2). Stage A runs on the list (the kernels of
 // mpcgpu_calc_posteriors), the dense matrices are rebuilt from the candidate lists (every cell with Score >= MIN_SPARSE_SCORE, also
@@ -828,7 +767,7 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 		if (rc != 2) return rc;
 	}
 	u32 chunk = 256; // pairs per stage-A call: their dense matrices (LX*LY floats each) live together
-	struct KeepList { mpcgpu_ctx *c; ~KeepList() { c->ap_keep = false; } } keep_guard{c};
+	KeepList keep_guard{c};
 	c->ap_keep = true;
 	c->ap_x.assign(seq1, seq1 + npairs); c->ap_y.assign(seq2, seq2 + npairs);
 	for (u32 q0 = 0; q0 < npairs;) {
@@ -868,42 +807,10 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 		c->last_post_cells = 0; // several matrices: not what mpcgpu_get_last_post hands out
 		if (all_wave) {
 			// one launch: parameters in, {length, score, path} out through page-locked memory
-			const u64 rstride = ((u64)8 + Lsum_max + 7) & ~7ull;
-			const u64 o_par = 0, o_res = o_par + (u64)nq * sizeof(AlnParams), bytes = o_res + (u64)nq * rstride;
-			HIPCHK(c, c->h_ap.ensure(bytes));
+			HIPCHK(c, c->h_ap.ensure((u64)nq * (sizeof(AlnParams) + aln_rec_stride(Lsum_max))));
 			HIPCHK(c, c->d_aln_rev.ensure_grow((u64)nq * Lsum_max + 16));
-			char *h = c->h_ap.as<char>();
-			AlnParams *ap = (AlnParams *)(h + o_par);
-			for (u32 q = 0; q < nq; ++q) {
-				char *r = h + o_res + (u64)q * rstride;
-				ap[q].post = c->d_aln_post.as<float>() + off[q];
-				ap[q].LX = c->len[seq1[q0 + q]]; ap[q].LY = c->len[seq2[q0 + q]];
-				ap[q].tb = nullptr; ap[q].rev = c->d_aln_rev.as<char>() + (u64)q * Lsum_max;
-				ap[q].pathlen = (u32 *)r; ap[q].score = (float *)(r + 4); ap[q].path = r + 8;
-			}
-			const size_t smem = (size_t)(LXmax + 1) * MPC_ALNW_ROWBYTES + 16;
-			if (smem > c->aln_smem_set[3]) {
-				(void)hipFuncSetAttribute((const void *)calc_aln_wave_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-				c->aln_smem_set[3] = smem;
-			}
-			TimedSpan ts;
-			if (span_begin(c, 8, &ts)) return 1;
-			MPC_LAUNCH(calc_aln_wave_batch_kernel, nq, 64, smem, c->stream, (const AlnParams *)ap);
-			HIPCHK(c, hipGetLastError());
-			if (span_end(c, &ts)) return 1;
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			for (u32 q = 0; q < nq; ++q) {
-				const char *r = h + o_res + (u64)q * rstride;
-				u32 n_path;
-				memcpy(&n_path, r, 4);
-				if (n_path > ap[q].LX + ap[q].LY) return fail(c, "mpcgpu_align_pairs: path length %u out of range (internal error)", n_path);
-				pathlens[q0 + q] = n_path;
-				float sc;
-				memcpy(&sc, r + 4, 4);
-				if (scores) scores[q0 + q] = sc;
-				if (ea) ea[q0 + q] = sc / (float)std::min(ap[q].LX, ap[q].LY); // alignpairflat.cpp:18 (uint -> float, IEEE divide)
-				memcpy(paths + (u64)(q0 + q) * path_stride, r + 8, n_path);
-			}
+			AlnParams *ap = c->h_ap.as<AlnParams>();
+			if (align_wave_batch(c, nq, seq1 + q0, seq2 + q0, off.data(), LXmax, Lsum_max, ap, (char *)(ap + nq), nullptr, path_stride, paths + (u64)q0 * path_stride, pathlens + q0, scores ? scores + q0 : nullptr, ea ? ea + q0 : nullptr)) return 1;
 		} else {
 			for (u32 q = 0; q < nq; ++q) {
 				const u32 LX = c->len[seq1[q0 + q]], LY = c->len[seq2[q0 + q]];
@@ -931,7 +838,7 @@ int mpcgpu_get_list_sparse(mpcgpu_ctx *c, uint32_t q, uint32_t *nnz, uint32_t *o
 	u32 ql = q;
 	if (!c->ap_x.empty()) {
 		if (q >= c->ap_x.size()) return fail(c, "mpcgpu_get_list_sparse: no list stage holds pair %u", q);
-		struct KeepList { mpcgpu_ctx *c; ~KeepList() { c->ap_keep = false; } } keep_guard{c};
+		KeepList keep_guard{c};
 		c->ap_keep = true;
 		bool inside = q >= c->list_q0 && q - c->list_q0 < c->list_x.size();
 		if (inside && !c->have_shard && want_record) { // the general stage on the window's list packs the records

@@ -56,17 +56,17 @@ from muscle_amd._lib import MpcGpu, MpcGpuError
 from muscle_amd.synth import make_family
 
 # ---- the dispatcher's limits ------------------------------------------------------------------------------------------------
-PAIRS_SMALL_MAX = 64            # mpcgpu_joins.inc:826  npairs <= 64 && MPCGPU_PAIRS_SMALL -> align_pairs_small
-LONG_MIN = 64 * 12 + 1          # mpcgpu_joins.inc:676, mpcgpu_stage_a.inc:59  MPCGPU_FB_LONG_MIN, clamped to [2, 64 * HMAX + 1]
+PAIRS_SMALL_MAX = 64            # mpcgpu_joins.inc: mpcgpu_align_pairs  npairs <= 64 && MPCGPU_PAIRS_SMALL -> align_pairs_small
+LONG_MIN = 64 * 12 + 1          # mpcgpu_stage_a.inc: stage_a_geom()  MPCGPU_FB_LONG_MIN, clamped to [2, 64 * HMAX + 1]
 HMAX = 16                       # kernels_fb.h:47  MPC_HMAX
-ALNW_MAXW = 512                 # kernels_aln.h:107  MPC_ALNW_MAXW: LY + 1 <= 512 for the one-wave alignment (mpcgpu_joins.inc:681)
-ALNW_ROWBYTES = 256             # kernels_aln.h:108  MPC_ALNW_ROWBYTES: (LX + 1) * 256 + 16 <= 160 KB (mpcgpu_joins.inc:681)
+ALNW_MAXW = 512                 # kernels_aln.h:107  MPC_ALNW_MAXW: LY + 1 <= 512 for the one-wave alignment (mpcgpu_joins.inc: align_pairs_small)
+ALNW_ROWBYTES = 256             # kernels_aln.h:108  MPC_ALNW_ROWBYTES: (LX + 1) * 256 + 16 <= 160 KB (mpcgpu_joins.inc: align_pairs_small)
 LDS_BYTES = 160 * 1024
-POST_ROWS_LDS = 150 * 1024      # mpcgpu_joins.inc:684, mpcgpu_stage_a.inc:238-239  the row-list finishing kernel's LDS arrays
-POST_SORT_CAP = 1024            # mpcgpu_stage_a.inc:239  MPCGPU_POST_SORT_CAP default
-CAND_PER_ROW = 12               # mpcgpu_joins.inc:686, mpcgpu_stage_a.inc:69  MPCGPU_CAND_PER_ROW
-CAND_FLOOR = 1024               # mpcgpu_joins.inc:686, mpcgpu_stage_a.inc:70
-CHUNK = 256                     # mpcgpu_joins.inc:830  pairs per stage-A call of the general path
+POST_ROWS_LDS = 150 * 1024      # mpcgpu_stage_a.inc: post_rows_fits()  the row-list finishing kernel's LDS arrays
+POST_SORT_CAP = 1024            # mpcgpu_stage_a.inc: stage_a()  MPCGPU_POST_SORT_CAP default
+CAND_PER_ROW = 12               # mpcgpu_stage_a.inc: stage_a_geom()  MPCGPU_CAND_PER_ROW
+CAND_FLOOR = 1024               # mpcgpu_stage_a.inc: stage_a_geom()
+CHUNK = 256                     # mpcgpu_joins.inc: mpcgpu_align_pairs  pairs per stage-A call of the general path
 QUAD_MAXW = 4096                # mpcgpu_joins.inc:13-14  (W + 255) / 256 * 64 <= 1024 threads
 LONG_H = 7                      # mpcgpu.cpp:381  MPC_LONG_H (MPCGPU_FB_LONG_H = 4: MPC_LONG_H_SMALL, 1: one row per lane)
 WAVE, QUAD, LDSROWS = "one wave", "waves, rows in registers", "rows in LDS"
@@ -116,7 +116,7 @@ def capc_of(lens, env):
 
 
 def regrowths(lens, cand, env):
-    """stage A's overflow retries on one batch (mpcgpu_stage_a.inc:478-491): the room doubles, up to LXmax * LYmax"""
+    """stage A's overflow retries on one batch (mpcgpu_stage_a.inc: stage_a()): the room doubles, up to LXmax * LYmax"""
     capc, n = capc_of(lens, env), 0
     full = max(a for a, _ in lens) * max(b for _, b in lens)
     while max(cand) > capc:
@@ -127,7 +127,7 @@ def regrowths(lens, cand, env):
 
 def predict(lens, env, cand=None):
     """the path of mpcgpu_align_pairs for pairs of these (LX, LY) under env: "short", "overflow" (short list whose candidate list
-    overflowed: the general path redoes it; needs the oracle's candidate counts) or "general" (mpcgpu_joins.inc:676-686, 826)"""
+    overflowed: the general path redoes it; needs the oracle's candidate counts) or "general" (mpcgpu_joins.inc: align_pairs_small, mpcgpu_align_pairs)"""
     n = len(lens)
     if not (1 <= n <= PAIRS_SMALL_MAX and env_int(env, "MPCGPU_PAIRS_SMALL", 1) != 0):
         return "general"
@@ -143,7 +143,7 @@ def predict(lens, env, cand=None):
 
 
 def post_rows_ok(lens, env):
-    """stage A takes the row-list finishing kernel (mpcgpu_stage_a.inc:238-239), which the general path needs"""
+    """stage A takes the row-list finishing kernel (mpcgpu_stage_a.inc: post_rows_fits()), which the general path needs"""
     if env.get("MPCGPU_POST") == "sort":
         return False
     LXm, LYm = max(a for a, _ in lens), max(b for _, b in lens)
@@ -152,7 +152,7 @@ def post_rows_ok(lens, env):
 
 def chunks_of(n, env):
     """the general path's chunks [(q0, nq)]: 256 pairs; MPCGPU_SCRATCH_GB=0 gives stage A one pair per batch, so the first chunk
-    halves down to one pair and every later chunk is one pair (mpcgpu_joins.inc:830-845, mpcgpu_stage_a.inc:125-129)"""
+    halves down to one pair and every later chunk is one pair (mpcgpu_joins.inc: mpcgpu_align_pairs; mpcgpu_stage_a.inc: prepare_batch())"""
     size = 1 if env_int(env, "MPCGPU_SCRATCH_GB", 32) == 0 else CHUNK
     return [(q0, min(size, n - q0)) for q0 in range(0, n, size)]
 

@@ -8,11 +8,12 @@ relax seeded from the same matrices (Run.deep; a run of fewer than three sequenc
 A pair sub-range is read through its shard: the three ranges [0,k0) [k0,k1) [k1,N) are exported, imported as one store and compared.
 
 predict() restates the dispatcher from sequence lengths, the pair range, the environment and the oracle's candidate counts: long_min
-(:59), the bin of every pair (:156, :210), the row-block instantiation (:293-300), the first candidate room and its doublings up to
-LXmax * LYmax (:69-70, :478-486), the finishing kernel and its LDS bytes (:238-239, :397-399, :427-429), per_pair / bmax / batches of
-equal size (:113-129), shard replacements (:500-514), and from these the order of launches (:454-531) and the launch counts per timer
+(stage_a_geom), the bin of every pair (build_chains, prepare_batch), the row-block instantiation (launch_fb_row_blocks), the first candidate
+room and its doublings up to LXmax * LYmax (stage_a_geom, stage_a's overflow retry), the finishing kernel and its LDS bytes (post_rows_fits,
+launch_post_rows, fill_post), per_pair / bmax / batches of equal size (prepare_batch), shard replacements (pack_batch), and from these the
+order of launches (stage_a's loop) and the launch counts per timer
 family (0: one per non-empty single bin, chain bin and the row-block bin, per batch and attempt; 1: one finishing kernel per attempt
-and one pack per batch). Whether a pair under long_min runs in fb_chain_kernel or alone in fb_kernel depends on chain_vcap (:95-110:
+and one pack per batch). Whether a pair under long_min runs in fb_chain_kernel or alone in fb_kernel depends on ChainPlan::vcap (chain_plan:
 occupancy and free memory), which the host cannot restate: the predictor fixes the SUM per batch and bin, and exactly "all chained" /
 "none chained" where Run.chain says so (MPCGPU_FB_CHAIN=0, Mega, or MPCGPU_FB_CHAIN_GRADE=0 with the default scratch budget and
 lengths far inside the room). The batch budget is min(MPCGPU_SCRATCH_GB, 40 % of free memory): every run must batch the same way at
@@ -70,11 +71,11 @@ from _align_pairs import bits, capc_of, env_int, long_min_of, post_rows_ok, regr
 from muscle_amd._lib import MpcGpu
 
 LONG_H, LONG_H_SMALL = 7, 4     # mpcgpu.cpp:381-382
-SCRATCH_GB = 32                 # mpcgpu_stage_a.inc:125
-BMAX = 1 << 22                  # mpcgpu_stage_a.inc:127
-LDS_CAP = 150 * 1024            # mpcgpu_stage_a.inc:239, :398
+SCRATCH_GB = 32                 # mpcgpu_stage_a.inc: scratch_budget()
+BMAX = 1 << 22                  # mpcgpu_stage_a.inc: prepare_batch()
+LDS_CAP = 150 * 1024            # mpcgpu_stage_a.inc: post_rows_fits(), launch_post_rows()
 FREE_MIN = {"gpu": 64 << 30, "emu": 4 << 30}  # free device memory a run may count on: a quarter of an MI355X; tests/emu/hip_emu.h:233
-MAX_LONG_PAIRS = 16             # mpcgpu_stage_a.inc:299 with cus >= 2
+MAX_LONG_PAIRS = 16             # mpcgpu_stage_a.inc: launch_fb_row_blocks() with cus >= 2
 MAX_GPU_CELLS = 10 ** 9         # the oracle's DP cells over the GPU table
 
 
@@ -154,7 +155,7 @@ def oracle_relax(seqs, want, iters=2):
 
 # ---- the predictor ----------------------------------------------------------------------------------------------------------
 def post_lds(LXmax, LYmax, capc, env):
-    """("rows" | "sort", dynamic LDS bytes, list entries in LDS) of the finishing kernel (mpcgpu_stage_a.inc:238-239, :393-399, :427-429)"""
+    """("rows" | "sort", dynamic LDS bytes, list entries in LDS) of the finishing kernel (mpcgpu_stage_a.inc: post_rows_fits(), launch_post_rows(), fill_post())"""
     cap_env = max(env_int(env, "MPCGPU_POST_SORT_CAP", A.POST_SORT_CAP), 2)
     if post_rows_ok([(LXmax, LYmax)], env):
         fixed = ((LXmax + 2 + 2 * (LYmax + 2)) * 4 + 7) & ~7
@@ -384,7 +385,7 @@ def cases(size):
     out.append(Case("overflow_middle", [Run("middle batch", fam[:2] + ["A" * 60, "A" * 100] + fam[2:], env, retries=1, dropped=True)]))
     out.append(Case("overflow_last", [Run("last batch", fam + ["A" * 60, "A" * 100], env, retries=1, retry_at=9, dropped=False)]))
     # ---- the same with batches of many pairs, under block_hmm(): the room doubles, per_pair doubles, and the batch is redone SMALLER
-    # (mpcgpu_stage_a.inc:486-490: prepare(done, cur) sizes it anew; the dropped next batch began at another pair). The room is
+    # (mpcgpu_stage_a.inc, stage_a()'s overflow retry: prepare_batch(.., done, cur) sizes it anew; the dropped next batch began at another pair). The room is
     # k x the longest sequence for every pair, a pair stores at most 100 cells per row, and a batch of B pairs under 1 GB has a room of about
     # 1 GB / 24 / B: so one dense pair of a x (a + 59) residues (60 equally likely offsets: 60 a candidates, P = 1 / 60) among short
     # poly-A sequences, whose pairs with the long ones store nothing (thousands of offsets)
