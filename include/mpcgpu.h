@@ -199,7 +199,10 @@ int mpcgpu_post_scores(mpcgpu_ctx *ctx, uint32_t LX, uint32_t LY, uint32_t ncand
 
 /* Posterior-DP alignment of one dense LX x LY matrix resident in HOST memory: replaces
  * CalcAlnFlat (calcalnflat.cpp:6-46) + TraceBackFlat (tracebackflat.cpp:3-37), tie order of
- * best3.h:5-28. path receives the B/X/Y string (capacity >= LX+LY), not NUL-terminated. */
+ * best3.h:5-28. path receives the B/X/Y string (capacity >= LX+LY), not NUL-terminated.
+ * Limits: none on the columns from the kernels (a matrix wider than the two DP rows the LDS holds, LY + 1 > ~20 470, is swept in
+ * column tiles: same cells, same comparisons, same letters); the matrix (4 * LX * LY bytes) and its traceback letters
+ * ((LX + 1) * (LY + 1) bytes) must fit device memory. */
 int mpcgpu_calc_aln(mpcgpu_ctx *ctx, const float *post, uint32_t LX, uint32_t LY,
                     char *path, uint32_t *pathlen, float *score);
 
@@ -267,8 +270,15 @@ int mpcgpu_align_msas(mpcgpu_ctx *ctx, uint32_t npairs, const uint32_t *seq1, co
  * The sparse matrices of the same pairs (AlignPairFlat_SparsePost) are then available through mpcgpu_get_list_sparse.
  * Like every stage-A call on a context, this one takes the context's scratch and INVALIDATES the all-pairs store the context may
  * hold (mpcgpu_build_store / mpcgpu_store_import): callers that interleave pair lists with a consistency run use a context of
- * their own for the lists (the drop-in's join contexts). A list is cut into chunks that one stage-A batch serves (halved as
- * often as needed); sequences beyond ~12 000 residues are refused (error, not a fallback). */
+ * their own for the lists (the drop-in's join contexts). A list is cut into chunks that one stage-A batch serves and whose dense
+ * matrices fit the device together (halved as often as needed, down to one pair).
+ * Limits: a pair must satisfy the reference's own test, double(LX) * double(LY) * 5 + 100 <= INT_MAX (calcposteriorflat.cpp:54-61,
+ * about 20 724 x 20 724, or 7 000 x 60 000) — a list with a pair beyond it is refused before any device work, with an error that names
+ * both lengths and the bound — and what stage A asks of the lengths (65 535 positions per sequence once the row sequence takes the
+ * row-block kernels; mpcgpu_set_seqs_registry tests no pairs, the calls that receive them do). A list whose sequences do not fit the
+ * row-list finishing kernel (roughly LXmax + 2 * LYmax > 36 344: sequences beyond ~12 000 residues) is finished by the sort-based
+ * kernel and its dense posteriors are built from the raw candidate lists: same bits. MPCGPU_POST=sort forces the sort-based kernel on
+ * lists that would fit and is refused here (error, not a fallback). */
 int mpcgpu_align_pairs(mpcgpu_ctx *ctx, uint32_t npairs, const uint32_t *seq1, const uint32_t *seq2, uint32_t path_stride,
                        char *paths, uint32_t *pathlens, float *scores, float *ea);
 /* MySparseMx::FromPost (mysparsemx.cpp:115-152) of pair q of the LAST list stage on this context (mpcgpu_align_pairs of at most 256

@@ -419,7 +419,8 @@ class MpcGpu:
         return np.float32(ea.value), off, val[:2 * nnz.value].copy()
 
     def calc_aln(self, post):
-        """post: (LX, LY) float32 dense matrix in host memory -> (path str of B/X/Y, score)"""
+        """post: (LX, LY) float32 dense matrix in host memory -> (path str of B/X/Y, score). Any number of columns: beyond ~20 470 the
+        DP rows are swept in column tiles (MPCGPU_ALN_KERNEL=4 forces that kernel at any size)."""
         post = np.ascontiguousarray(post, np.float32)
         LX, LY = post.shape
         path = np.empty(LX + LY, np.uint8)
@@ -464,7 +465,9 @@ class MpcGpu:
         return [(paths[q * stride:q * stride + int(plen[q])].tobytes().decode(), float(sc[q])) for q in range(nj)]
 
     def align_pairs(self, seq1, seq2, sparse=False):
-        """AlignPairFlat for a list of pairs of registered sequences -> [(path, score, ea)] (+ (off, val) per pair with sparse=True)"""
+        """AlignPairFlat for a list of pairs of registered sequences -> [(path, score, ea)] (+ (off, val) per pair with sparse=True).
+        Every pair with LX * LY * 5 + 100 <= INT_MAX (the reference's limit, ~20 724 x 20 724) whose lengths stage A takes; a list with
+        a pair beyond it raises MpcGpuError naming both lengths before anything runs, and the context stays usable."""
         s1, s2 = np.ascontiguousarray(seq1, np.uint32), np.ascontiguousarray(seq2, np.uint32)
         n = len(s1)
         stride = int(max(int(self.lens[a]) + int(self.lens[b]) for a, b in zip(s1, s2))) if n else 1

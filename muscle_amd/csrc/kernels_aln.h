@@ -16,6 +16,7 @@
 // progressive stage can stay on the device, not because one call beats a CPU.
 #pragma once
 #include "kernels_fb.h" // candidate key layout (dense_post_kernel)
+#include "kernels_post.h" // mpc_key_shift
 #include "device_math.h"
 
 
@@ -282,6 +283,138 @@ __global__ void __launch_bounds__(256) dense_post_kernel(DensePostParams p)
 		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
 		M[(u64)row * LY + col] = __uint_as_float((u32)v);
 	}
+}
+
+// The same matrix from the RAW candidate lists the sort-based post_kernel leaves behind (kernels_post.h: it copies (key, score
+// bits) into its own sort buffer and never writes the list back), for lists that do not fit post_rows_kernel's LDS arrays: pairs of
+// more than ~12 000 residues. The probability is formed here, with post_rows_kernel's function and operand (mpc_score_to_prob on
+// the score bits, the stage's use_fma), so a cell holds the bits the row-list route would have left in the list. A 20 000 x 20 000
+// matrix is 1.6 GB: the host zeroes the chunk's matrices with one memset on the stream, and the scatter runs on a grid of
+// (pairs) x (slabs of a pair's list). An overflowed list writes nothing, as above.
+struct DensePostRawParams {
+	DensePostParams d;
+	int use_fma;
+	u32 slabs; // workgroups per pair: workgroup b serves slab b % slabs of pair b / slabs
+};
+
+__global__ void __launch_bounds__(256) dense_post_raw_kernel(DensePostRawParams p)
+{
+	const u32 q = blockIdx.x / p.slabs, slab = blockIdx.x % p.slabs;
+	const u32 LX = p.d.seq_len[p.d.pair_x[q]], LY = p.d.seq_len[p.d.pair_y[q]];
+	const u32 c = p.d.cand_cnt[q];
+	if (c > p.d.capc) return;
+	float *M = p.d.out + p.d.out_off[q];
+	const u32 kshift = mpc_key_shift(LX, p.d.long_min);
+	const u64 *cand = p.d.cand + (u64)q * p.d.capc;
+	for (u32 e = slab * blockDim.x + threadIdx.x; e < c; e += p.slabs * blockDim.x) {
+		const u64 v = cand[e];
+		const u32 key = (u32)(v >> 32);
+		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
+		const float pr = mpc_score_to_prob(__uint_as_float((u32)v), p.use_fma);
+		if (row < LX && col < LY) M[(u64)row * LY + col] = pr; // (a key is a cell of the matrix: the test only keeps a damaged list inside it)
+	}
+}
+
+// ---- matrices wider than the LDS holds two DP rows of (calc_aln_kernel's limit: LY + 1 <= ~20 470 columns) ------------------
+// calc_aln_kernel with the columns swept in tiles of `tile` columns: a tile runs all LX rows with its two DP rows in LDS, then
+// the next tile does, and what crosses a tile's left edge is one value per row, S(i, a-1) of the tile's first column a: the
+// diagonal input of that column in row i+1 and the value the row's prefix maximum starts from (S(i,j) = max(T_j, S(i,j-1)),
+// so a prefix maximum seeded with S(i, a-1) is the sequential recurrence; max is exact). The boundary column goes through two
+// arrays of LX + 1 floats in device memory, one read and one written per tile: a tile reads what the tile before it wrote many
+// workgroup barriers earlier (every row ends with one, and __syncthreads orders the workgroup's global accesses as it orders
+// its LDS accesses — calc_aln_quad_kernel's traceback bytes rely on the same). Same cells, same comparisons, same tie order,
+// same 'B' / 'X' / 'Y' bytes, same walk back as calc_aln_kernel; no limit on the columns.
+__global__ void __launch_bounds__(MPC_ALN_THREADS) calc_aln_tiled_kernel(AlnParams p, float *bnd, u32 tile)
+{
+	MPC_DYN_SMEM(smem_raw);
+	const u32 LX = p.LX, LY = p.LY, W = LY + 1;
+	float *rows = (float *)smem_raw;             // 2 * (tile + 1): slot 0 = the column left of the tile, slot l + 1 = column a + l
+	float *wmax = rows + 2 * ((u64)tile + 1);    // one per wave
+	u32 *s_n = (u32 *)(wmax + MPC_ALN_THREADS / 64);
+	const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	float last = 0.0f; // S(LX, LY)
+	u32 t = 0;
+	for (u32 a = 0; a < W; a += tile, ++t) {
+		const u32 n = W - a < tile ? W - a : tile; // columns [a, a + n)
+		const float *bin = bnd + (u64)(t & 1u) * (LX + 1);       // S(., a - 1): written by the tile before (unused when a == 0)
+		float *bout = bnd + (u64)((t & 1u) ^ 1u) * (LX + 1);     // S(., a + n - 1)
+		const u32 C = (n + MPC_ALN_THREADS - 1) / MPC_ALN_THREADS;
+		const u32 l0 = tid * C, l1 = (l0 + C < n) ? l0 + C : n; // my columns a + [l0, l1)
+		float *oldr = rows, *newr = rows + tile + 1;
+		for (u32 l = l0; l < l1; ++l) { oldr[l + 1] = 0.0f; p.tb[a + l] = 'Y'; } // calcalnflat.cpp:15-19
+		if (tid == 0) { oldr[0] = 0.0f; bout[0] = 0.0f; }
+		float left = (a && LX) ? bin[1] : 0.0f; // S(i, a - 1) of the row at hand, loaded one row ahead
+		__syncthreads();
+		for (u32 i = 1; i <= LX; ++i) {
+			const float *prow = p.post + (u64)(i - 1) * LY;
+			char *tbrow = p.tb + (u64)i * W;
+			const float left_i = left;
+			left = a ? bin[i < LX ? i + 1 : LX] : 0.0f;
+			// pass 1: maximum of T over my columns
+			float run = 0.0f; // T_j >= 0 always (X >= 0), and S(i,0) = 0
+			for (u32 l = l0; l < l1; ++l) {
+				const u32 j = a + l;
+				if (j == 0) continue;
+				const float B = oldr[l] + prow[j - 1];
+				const float X = oldr[l + 1];
+				const float T = B >= X ? B : X;
+				run = T >= run ? T : run;
+			}
+			// workgroup-wide exclusive prefix maximum of the per-thread maxima, over S(i, a - 1)
+			const float incl = mpc_wave_scan_max_nonneg(run);
+			float excl = mpc_lane_up1(incl);
+			if (lane == 0) excl = 0.0f;
+			if (lane == 63) wmax[wave] = incl;
+			__syncthreads();
+			for (u32 w = 0; w < wave; ++w) { const float o = wmax[w]; excl = o >= excl ? o : excl; }
+			excl = left_i >= excl ? left_i : excl;
+			// pass 2: S and the traceback letters
+			float Y = excl; // S(i, a + l0 - 1)
+			for (u32 l = l0; l < l1; ++l) {
+				const u32 j = a + l;
+				if (j == 0) { newr[1] = 0.0f; tbrow[0] = 'X'; Y = 0.0f; continue; } // calcalnflat.cpp:23-25
+				const float B = oldr[l] + prow[j - 1];
+				const float X = oldr[l + 1];
+				const bool bx = B >= X;            // best3.h:9
+				const float T = bx ? B : X;
+				const bool ty = T >= Y;            // best3.h:11 / :21
+				const float S = ty ? T : Y;
+				newr[l + 1] = S;
+				tbrow[j] = ty ? (bx ? 'B' : 'X') : 'Y';
+				Y = S;
+			}
+			if (l0 < n && l1 == n) { bout[i] = Y; last = Y; } // the tile's last column: the next tile's left edge
+			if (tid == 0) newr[0] = left_i;
+			__syncthreads();
+			float *tmp = oldr; oldr = newr; newr = tmp;
+		}
+		if (LX == 0) __syncthreads();
+	}
+	// the score lives in the thread that owned column LY of the last tile
+	float *s_score = wmax; // (free now)
+	{
+		const u32 a = ((W - 1) / tile) * tile, n = W - a;
+		const u32 C = (n + MPC_ALN_THREADS - 1) / MPC_ALN_THREADS;
+		const u32 l0 = tid * C, l1 = (l0 + C < n) ? l0 + C : n;
+		if (l0 < n && l1 == n) *s_score = last;
+	}
+	__syncthreads();
+	// TraceBackFlat (tracebackflat.cpp:3-37)
+	if (tid == 0) {
+		*p.score = *s_score;
+		int i = (int)LX, j = (int)LY;
+		u32 n = 0;
+		while (i != 0 || j != 0) {
+			const char c = p.tb[(u64)i * W + j];
+			p.rev[n++] = c;
+			if (c == 'B') { --i; --j; } else if (c == 'X') --i; else --j;
+		}
+		*s_n = n;
+		*p.pathlen = n;
+	}
+	__syncthreads();
+	const u32 n = *s_n;
+	for (u32 k = tid; k < n; k += MPC_ALN_THREADS) p.path[k] = p.rev[n - 1 - k];
 }
 
 // ---- several wavefronts, previous row in registers (matrices wider than one wave holds: the joins near the root) ---------

@@ -154,9 +154,9 @@ struct mpcgpu_ctx {
 	u64 total_entries = 0;
 	u32 max_nnz = 0, max_len = 0;
 	HostBuf h_bp_in, h_aln_res;
-	size_t aln_smem_set[4] = {0, 0, 0, 0}; // largest dynamic LDS each CalcAlnFlat kernel has been allowed so far
+	size_t aln_smem_set[5] = {0, 0, 0, 0, 0}; // largest dynamic LDS each CalcAlnFlat kernel has been allowed so far
 	DevBuf d_tile_next, d_bp_in, d_aln_res, d_bp_seq, d_bp_map, d_bp_off, d_bp_coff, d_bp_keys, d_bp_vals, d_bp_tmp, d_bp_runs;
-	DevBuf d_tiles, d_pad, d_pos, d_aln_post, d_aln_tb, d_aln_rev;
+	DevBuf d_tiles, d_pad, d_pos, d_aln_post, d_aln_tb, d_aln_rev, d_aln_bnd;
 	bool have_pad = false;       // variable-size dense records + relax_var_kernel (else: slabs + gather relax)
 	u32 pad_lcap1 = 0;           // longest sequence (LDS scratch of var_build_kernel)
 	DevBuf d_rec_off, d_sizes, d_tilefit;
@@ -646,7 +646,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->h_bp_in.release();
 	c->h_aln_res.release();
 	c->h_ap.release();
-	c->d_ap_off.release();
+	c->d_ap_off.release(); c->d_aln_bnd.release();
 	c->d_chain_first.release(); c->d_chain_cnt.release();
 	c->d_bx_n.release(); c->d_by_n.release(); c->d_order_n.release(); c->d_chain_first_n.release(); c->d_chain_cnt_n.release();
 	c->d_rects.release(); c->d_need.release(); c->d_exp_klist.release(); c->d_exp_valbase.release();
@@ -719,8 +719,9 @@ static int set_seqs_impl(mpcgpu_ctx *c, uint32_t n, const uint8_t *const *seqs, 
 		}
 		if (lens[i] > maxl) { max2 = maxl; maxl = lens[i]; } else if (lens[i] > max2) max2 = lens[i];
 	}
-	// calcposteriorflat.cpp:54-61
-	if (double(maxl) * double(max2) * 5 + 100 > double(INT_MAX))
+	// calcposteriorflat.cpp:54-61, on the longest pair of the all-pairs table. A registry serves explicit pair lists: its calls test
+	// the pairs they are given (stage_a, mpcgpu_align_pairs), so it may hold a 60 000-residue sequence beside a 12 000-residue one
+	if (with_pairs && double(maxl) * double(max2) * 5 + 100 > double(INT_MAX))
 		return fail(c, "HMM overflow, sequence lengths %u, %u (max ~21k)", maxl, max2);
 	std::vector<u8> code;
 	std::vector<u64> off(n + 1, 0);

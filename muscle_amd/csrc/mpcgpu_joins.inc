@@ -7,15 +7,19 @@ static int run_calc_aln(mpcgpu_ctx *c, const float *d_post, uint32_t LX, uint32_
 	// one wavefront with the previous row in registers and the traceback codes in LDS when the matrix is small enough
 	// (the progressive joins and refinement rounds of L~400 families are), else the workgroup kernel
 	const size_t smem_wave = (size_t)(LX + 1) * MPC_ALNW_ROWBYTES + 16;
-	const int pick = env_int("MPCGPU_ALN_KERNEL", 0); // 0 = by size, 1 = one wave, 2 = several waves, 3 = LDS rows
+	const int pick = env_int("MPCGPU_ALN_KERNEL", 0); // 0 = by size, 1 = one wave, 2 = several waves, 3 = LDS rows, 4 = LDS rows in column tiles
 	const bool wave = W <= MPC_ALNW_MAXW && smem_wave <= 160u * 1024u && (pick == 0 || pick == 1);
 	// several waves, 4 columns per thread, previous row in registers: up to 4096 columns
 	const u32 qthreads = (u32)((W + 4 * 64 - 1) / (4 * 64)) * 64;
 	const bool quad = !wave && qthreads <= 1024 && (pick == 0 || pick == 2);
 	const u32 qrows = quad ? (u32)std::min<u64>((u64)LX + 1, (150u * 1024u) / qthreads) : 0;
-	const size_t smem = wave ? smem_wave : quad ? (size_t)MPC_ALNQ_HDR + (size_t)qrows * qthreads : (size_t)(2 * W + MPC_ALN_THREADS / 64 + 4) * 4;
-	if (smem > 160u * 1024u)
-		return fail(c, "mpcgpu_calc_aln: %u columns exceed the LDS-resident DP rows of this build", LY);
+	// two DP rows of LY + 1 floats in LDS; wider than that (or MPCGPU_ALN_KERNEL=4): the same rows in column tiles, the tile's left
+	// edge carried through device memory (calc_aln_tiled_kernel). MPCGPU_ALN_TILE: columns per tile (tests: several tiles of a small matrix)
+	const size_t smem_rows = (size_t)(2 * W + MPC_ALN_THREADS / 64 + 4) * 4;
+	const bool tiled = !wave && !quad && (pick == 4 || smem_rows > 160u * 1024u);
+	const u32 tile = tiled ? (u32)std::min<u64>(W, (u64)std::min(std::max(env_int("MPCGPU_ALN_TILE", 16384), 1), 16384)) : 0;
+	const size_t smem = wave ? smem_wave : quad ? (size_t)MPC_ALNQ_HDR + (size_t)qrows * qthreads : tiled ? (size_t)(2 * ((u64)tile + 1) + MPC_ALN_THREADS / 64 + 4) * 4 : smem_rows;
+	if (tiled) HIPCHK(c, c->d_aln_bnd.ensure_grow(2 * ((u64)LX + 1) * 4));
 	HIPCHK(c, c->d_aln_tb.ensure_grow(((u64)LX + 1) * (quad ? (u64)qthreads : W))); // letters per cell, or one byte per thread and row
 	HIPCHK(c, c->d_aln_rev.ensure_grow((u64)LX + LY));
 	// one result record {path length, score, path}: one copy back, one wait
@@ -26,17 +30,18 @@ static int run_calc_aln(mpcgpu_ctx *c, const float *d_post, uint32_t LX, uint32_
 	ap.tb = c->d_aln_tb.as<char>(); ap.rev = c->d_aln_rev.as<char>();
 	// the record is written straight into page-locked host memory (device-visible: hipHostMalloc): no copy back, one wait
 	ap.pathlen = c->h_aln_res.as<u32>(); ap.score = c->h_aln_res.as<float>() + 1; ap.path = c->h_aln_res.as<char>() + 8;
-	const int which = wave ? 0 : quad ? 1 : 2;
+	const int which = wave ? 0 : quad ? 1 : tiled ? 4 : 2;
 	if (smem > c->aln_smem_set[which]) { // raise the kernel's dynamic-LDS limit only when this call needs more than any before
-		(void)hipFuncSetAttribute(wave ? (const void *)calc_aln_wave_kernel : quad ? (const void *)calc_aln_quad_kernel : (const void *)calc_aln_kernel,
+		(void)hipFuncSetAttribute(wave ? (const void *)calc_aln_wave_kernel : quad ? (const void *)calc_aln_quad_kernel : tiled ? (const void *)calc_aln_tiled_kernel : (const void *)calc_aln_kernel,
 			hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 		c->aln_smem_set[which] = smem;
 	}
-	if (trace_on()) { fprintf(stderr, "[mpcgpu] calc_aln %u x %u: %s\n", LX, LY, wave ? "one wave" : quad ? "waves, rows in registers" : "rows in LDS"); fflush(stderr); }
+	if (trace_on()) { fprintf(stderr, "[mpcgpu] calc_aln %u x %u: %s\n", LX, LY, wave ? "one wave" : quad ? "waves, rows in registers" : tiled ? "rows in LDS, column tiles" : "rows in LDS"); fflush(stderr); }
 	TimedSpan ts_aln;
 	if (span_begin(c, 8, &ts_aln)) return 1;
 	if (wave) MPC_LAUNCH(calc_aln_wave_kernel, 1, 64, smem, c->stream, ap);
 	else if (quad) MPC_LAUNCH(calc_aln_quad_kernel, 1, qthreads, smem, c->stream, ap, qrows);
+	else if (tiled) MPC_LAUNCH(calc_aln_tiled_kernel, 1, MPC_ALN_THREADS, smem, c->stream, ap, c->d_aln_bnd.as<float>(), tile);
 	else MPC_LAUNCH(calc_aln_kernel, 1, MPC_ALN_THREADS, smem, c->stream, ap);
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts_aln)) return 1;
@@ -761,6 +766,12 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 		if (seq1[q] >= c->n || seq2[q] >= c->n) return fail(c, "mpcgpu_align_pairs: sequence index out of range in pair %u", q);
 		if ((u64)c->len[seq1[q]] + c->len[seq2[q]] > path_stride) return fail(c, "mpcgpu_align_pairs: path_stride %u too small for pair %u", path_stride, q);
 	}
+	// the reference's own limit on a dense posterior (calcposteriorflat.cpp:54-61), before any device work
+	for (u32 q = 0; q < npairs; ++q) {
+		const u32 LX = c->len[seq1[q]], LY = c->len[seq2[q]];
+		if (double(LX) * double(LY) * 5 + 100 > double(INT_MAX))
+			return fail(c, "mpcgpu_align_pairs: pair %u is too long for a dense posterior: LX=%u, LY=%u, LX*LY*5 + 100 exceeds INT_MAX = %d", q, LX, LY, INT_MAX);
+	}
 	HIPCHK(c, hipSetDevice(c->device));
 	if (npairs >= 1 && npairs <= 64 && env_int("MPCGPU_PAIRS_SMALL", 1)) {
 		const int rc = align_pairs_small(c, npairs, seq1, seq2, path_stride, paths, pathlens, scores, ea);
@@ -772,6 +783,15 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 	c->ap_x.assign(seq1, seq1 + npairs); c->ap_y.assign(seq2, seq2 + npairs);
 	for (u32 q0 = 0; q0 < npairs;) {
 		u32 nq = std::min<u32>(chunk, npairs - q0);
+		// the chunk's dense matrices live together in d_aln_post: a chunk whose matrices do not fit half of what is free (long pairs: 1.6 GB
+		// for 20 000 x 20 000) is halved like one that stage A has to split, down to a single pair
+		{
+			size_t freeb = 0, totb = 0;
+			HIPCHK(c, hipMemGetInfo(&freeb, &totb));
+			const u64 room = (u64)((freeb + c->d_aln_post.cap) * 0.5);
+			auto bytes_of = [&](u32 k) { u64 b = 0; for (u32 q = 0; q < k; ++q) b += (u64)c->len[seq1[q0 + q]] * c->len[seq2[q0 + q]] * 4; return b; };
+			while (nq > 1 && bytes_of(nq) > room) { nq = (nq + 1) / 2; chunk = nq; }
+		}
 		// the dense matrices below are rebuilt from the candidate lists ONE stage-A batch leaves behind: a chunk that stage A had to
 		// cut into several batches (long sequences, little free memory) is halved and run again, down to a single pair
 		for (;;) {
@@ -782,7 +802,10 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 			nq = (nq + 1) / 2;
 			chunk = nq;
 		}
-		if (!c->sa_post_rows)
+		// Without the row-list finishing kernel the candidate lists still hold the scores (post_kernel sorts a copy): the raw builder forms
+		// the probabilities itself. Only a list that does not FIT the row-list kernel goes that way; MPCGPU_POST=sort stays a refusal.
+		const char *post_mode = getenv("MPCGPU_POST");
+		if (!c->sa_post_rows && post_mode && !strcmp(post_mode, "sort"))
 			return fail(c, "mpcgpu_align_pairs: pair list with a sequence of more than ~12 000 residues (or MPCGPU_POST=sort): the row-list finishing kernel "
 				"whose candidate lists this entry point rebuilds the dense posteriors from does not take them");
 		// dense matrices
@@ -802,7 +825,20 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 		dp.pair_x = c->d_bx.as<u32>(); dp.pair_y = c->d_by.as<u32>(); dp.seq_len = c->d_seq_len.as<u32>();
 		dp.cand = c->d_cand.as<u64>(); dp.capc = c->sa_capc; dp.cand_cnt = c->d_cand_cnt.as<u32>(); dp.long_min = c->sa_long_min;
 		dp.out_off = c->d_ap_off.as<u64>(); dp.out = c->d_aln_post.as<float>();
-		MPC_LAUNCH(dense_post_kernel, nq, 256, 0, c->stream, dp);
+		if (c->sa_post_rows) MPC_LAUNCH(dense_post_kernel, nq, 256, 0, c->stream, dp);
+		else {
+			// zeroes by one memset on the stream, the scatter on (pairs) x (slabs of 256 candidates, as many as keep the chip busy)
+			DensePostRawParams rp;
+			rp.d = dp; rp.use_fma = c->use_fma;
+			rp.slabs = (u32)std::max<u64>(1, std::min<u64>(((u64)c->sa_capc + 255) / 256, ((u64)c->prop.multiProcessorCount * 8 + nq - 1) / nq));
+			if (trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs dense posteriors from raw candidates: %u pairs x %u slabs, %.1f MB\n", nq, rp.slabs, (double)off[nq] * 4 / 1048576.0); fflush(stderr); }
+			TimedSpan ts_dense;
+			if (span_begin(c, 5, &ts_dense)) return 1;
+			HIPCHK(c, hipMemsetAsync(c->d_aln_post.p, 0, off[nq] * 4, c->stream));
+			MPC_LAUNCH(dense_post_raw_kernel, nq * rp.slabs, 256, 0, c->stream, rp);
+			HIPCHK(c, hipGetLastError());
+			if (span_end(c, &ts_dense)) return 1;
+		}
 		HIPCHK(c, hipGetLastError());
 		c->last_post_cells = 0; // several matrices: not what mpcgpu_get_last_post hands out
 		if (all_wave) {

@@ -455,6 +455,7 @@ static int launch_post_batch(mpcgpu_ctx *c, const StageAGeom &g, bool post_rows,
 	} else {
 		PostParams pp;
 		const size_t psmem = fill_post(c, g, io, sort_cap, pp);
+		ensure_dyn_smem((const void *)post_kernel, psmem); // (beyond 64 KB only under a MPCGPU_POST_SORT_CAP of more than 4096 entries)
 		int pocc = 0;
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pocc, (const void *)post_kernel, 64, psmem) != hipSuccess || pocc < 1) pocc = 8;
 		if (psmem) pocc = std::max(1, std::min(pocc, (int)((152 * 1024) / psmem))); // as for post_rows_kernel above
@@ -551,6 +552,9 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 		c->have_shard = true;
 		return 0;
 	}
+	for (u64 k = 0; k < np; ++k) // calcposteriorflat.cpp:54-61, per pair (a registry holds sequences that never meet)
+		if (double(c->len[px[k]]) * double(c->len[py[k]]) * 5 + 100 > double(INT_MAX))
+			return fail(c, "mpcgpu_calc_posteriors: HMM overflow, sequence lengths %u, %u (max ~21k)", c->len[px[k]], c->len[py[k]]);
 	if (g.LXlong > MPC_KEY_COL_MASK_LONG || g.LYlong > MPC_KEY_COL_MASK_LONG)
 		return fail(c, "mpcgpu_calc_posteriors: a pair of %u x %u positions is beyond this build's limit of %u per sequence "
 			"once the row sequence is longer than %u", g.LXlong, g.LYlong, MPC_KEY_COL_MASK_LONG, g.long_min - 1);
