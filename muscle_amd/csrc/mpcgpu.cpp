@@ -220,8 +220,8 @@ struct mpcgpu_ctx {
 	std::vector<u8> v_shdr;                 // stage A: the shard's header as it is uploaded
 	std::vector<u8> v_hdr;                  // mpcgpu_store_import: a shard's header as it is read back
 	std::vector<u32> v_off, v_woff;         // build_var_store: block offsets of the n x n records / window records
-	std::vector<u32> v_words, v_out, v_w2, v_o2, v_okw; // relax_band: tile words and their statistics while the tiles are cut
-	HostBuf h_bt;             // relax_band's tile cutter: the small host <-> device transfers of a cut, page-locked (a copy into pageable memory
+	std::vector<u32> v_words, v_out, v_w2, v_o2, v_okw; // cut_band_tiles (mpcgpu_relax.inc): tile words and their statistics while the tiles are cut
+	HostBuf h_bt;             // the tile cutter's `cut`: the small host <-> device transfers of a cut, page-locked (a copy into pageable memory
 	                          // right after a launch was measured at 24 ms on an otherwise idle device: profiles/r10k)
 	DevBuf d_ap_off;
 	DevBuf d_chain_first, d_chain_cnt; // fb_chain_kernel's work list (kernels_fbc.h)
