@@ -61,7 +61,14 @@ int mpcgpu_set_hmm(mpcgpu_ctx *ctx, const float start[5], const float trans[25],
  * 1024, the only way beyond), which need both lengths <= 65535 (the reference's own limit is ~21k x 21k); the
  * consistency relax runs LDS-tiled while the records of a pair fit the CU's LDS (sequences of up to ~1000-2000 residues,
  * depending on how many cells a row stores; never beyond 4095) and through the gather kernel beyond —
- * mpcgpu_relax_info says which. */
+ * mpcgpu_relax_info says which.
+ * The size of the all-pairs store is bounded by device memory, not by an index: the row-indexed records are addressed by 32-bit
+ * block indices (16-byte blocks) INSIDE A SEGMENT, a run of whole Z slabs (the records (., Z) of all sequences) with a device
+ * allocation of its own; a store beyond 2^32 blocks (64 GiB; about 2 900 sequences of length 400) is cut into several
+ * (mpcgpu_plan_store_segments) and relaxed by the same band-tile kernel — mpcgpu_relax_info then names the number of segments.
+ * What still sends a store to the gather kernel: a sequence longer than 4095 or a record of more than 4095 blocks; n * n or the
+ * number of pairs >= 2^32; 2^32 or more stored posteriors in all (about 3 400 sequences of length 400); one Z slab alone of 2^32
+ * blocks (n * 4095 blocks: no n below 2^20). */
 int mpcgpu_set_seqs(mpcgpu_ctx *ctx, uint32_t n, const uint8_t *const *seqs, const uint32_t *lens);
 
 /* Structure-profile ("mega") emissions for stage A. Replaces the Mega statics a .mega input fills
@@ -109,6 +116,16 @@ int mpcgpu_pair_position(mpcgpu_ctx *ctx, uint32_t x, uint32_t y, uint64_t *pos)
  * contiguous ranges balanced by DP cells — the partition of rounds 1-5. Returns 0, or 2 when max_rects is too small. */
 int mpcgpu_plan_partition(uint32_t n, const uint32_t *lens, uint32_t world, uint32_t max_rects, uint32_t *rects,
                           uint32_t *nrects, uint64_t *rank_pos);
+
+/* The segments of a record store (host only, no context; the store build calls the same function). sizes: the n * n record sizes
+ * in 16-byte blocks, Z-MAJOR (sizes[Z * n + A] = record (A, Z)); limit_blocks: the most a segment may hold, 0 or anything above it = the layout's own
+ * limit, 2^32 - 1 (a record's start and a slab's end are 32-bit block indices inside their segment). The n Z slabs are cut into
+ * the fewest runs of consecutive slabs within the limit: segment g holds the slabs [z_first[g], z_first[g + 1]) and blocks[g]
+ * blocks; z_first has max_segs + 1 entries, blocks max_segs. *nsegs receives the number of segments. Returns 0; 1 for missing
+ * arguments; 2 when max_segs is too small (*nsegs is set: call again); 3 when one slab alone is larger than the limit (no
+ * segmentation exists: a store build falls back to the gather layout). */
+int mpcgpu_plan_store_segments(uint32_t n, const uint32_t *sizes, uint64_t limit_blocks, uint32_t max_segs, uint32_t *z_first,
+                               uint64_t *blocks, uint32_t *nsegs);
 
 /* Stage A for the pair range [k0,k1): replaces MPCFlat::CalcPosteriors' OpenMP loop
  * (mpcflat.cpp:239-251) over MPCFlat::CalcPosterior (calcposteriorflat.cpp:45-92), i.e.

@@ -21,7 +21,7 @@ SYMBOLS = [
     "mpcgpu_cons_iter", "mpcgpu_cons_commit", "mpcgpu_cons_commit_range", "mpcgpu_get_ea", "mpcgpu_get_nnz", "mpcgpu_get_sparse",
     "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
     "mpcgpu_work_get", "mpcgpu_synchronize", "mpcgpu_relax_info", "mpcgpu_shard_entries",
-    "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch",
+    "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
     "mpcgpu_group_transport", "mpcgpu_group_set_hmm", "mpcgpu_group_set_seqs", "mpcgpu_group_set_mega",
     "mpcgpu_group_calc_posteriors", "mpcgpu_group_cons_iter",
@@ -67,6 +67,7 @@ def load(lib_path=None):
     L.mpcgpu_set_pair_order.argtypes = [vp, u32, vp]
     L.mpcgpu_pair_position.argtypes = [vp, u32, u32, C.POINTER(u64)]
     L.mpcgpu_plan_partition.argtypes = [u32, vp, u32, u32, vp, C.POINTER(u32), vp]
+    L.mpcgpu_plan_store_segments.argtypes = [u32, vp, u64, u32, vp, vp, C.POINTER(u32)]
     L.mpcgpu_store_import_part.argtypes = [vp, u32, vp, vp, vp, vp, vp, u64, u64]
     L.mpcgpu_store_complete.argtypes = [vp]
     L.mpcgpu_store_info.argtypes = [vp, vp]
@@ -129,6 +130,26 @@ def plan_partition(lens, world, lib_path=None, L=None):
     if rc != 0:
         raise MpcGpuError("mpcgpu_plan_partition failed (%d)" % rc)
     return rects[:nr.value].copy(), [int(x) for x in pos]
+
+
+def plan_store_segments(n, sizes, limit_blocks=0, lib_path=None, L=None):
+    """The segments of a record store (include/mpcgpu.h: mpcgpu_plan_store_segments; host only, no device). sizes: the n * n
+    record sizes in blocks, Z-major. -> (z_first: nsegs + 1 slab numbers, blocks: nsegs block counts); raises where one slab
+    alone is larger than the limit."""
+    L = L or load(lib_path)
+    sizes = np.ascontiguousarray(sizes, np.uint32).ravel()
+    if sizes.size != n * n:
+        raise ValueError("plan_store_segments: %d sizes for n = %d" % (sizes.size, n))
+    cap = 16
+    while True:
+        zf, bl, ns = np.zeros(cap + 1, np.uint32), np.zeros(cap, np.uint64), C.c_uint32()
+        rc = L.mpcgpu_plan_store_segments(n, sizes.ctypes.data, limit_blocks, cap, zf.ctypes.data, bl.ctypes.data, C.byref(ns))
+        if rc == 2:
+            cap = ns.value
+            continue
+        if rc != 0:
+            raise MpcGpuError("mpcgpu_plan_store_segments failed (%d)%s" % (rc, ": a Z slab is larger than the segment limit" if rc == 3 else ""))
+        return [int(z) for z in zf[:ns.value + 1]], [int(b) for b in bl[:ns.value]]
 
 
 class MpcGroup:

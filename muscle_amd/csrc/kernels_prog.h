@@ -234,9 +234,7 @@ template <int CH, class PARAMS> // 64 * CH >= C2: columns a lane accumulates in 
 __device__ __forceinline__ void build_post_one_row(const PARAMS &p, u32 col1, u32 *lkey, float *lval)
 {
 	const u32 lane = threadIdx.x;
-	const u32 n = p.s.n;
 	const u32 npairs = p.n1 * p.n2;
-	const unsigned char *padb = (const unsigned char *)p.s.pad;
 	float acc[CH];
 #pragma unroll
 	for (int c = 0; c < CH; ++c) acc[c] = 0.0f; // buildpostflat.cpp:27-30
@@ -247,7 +245,7 @@ __device__ __forceinline__ void build_post_one_row(const PARAMS &p, u32 col1, u3
 		const u32 pos = valid ? p.c2p1[(u64)a * p.C1 + col1] : MPC_BPR_GAP;
 		const bool have = pos != MPC_BPR_GAP;
 		const u32 S = p.seq1[a], T = p.seq2[b];
-		const unsigned char *row0 = padb + 16 * ((u64)p.s.rec_off[mpc_rec_index(n, S, T)] + (have ? pos : 0u));
+		const unsigned char *row0 = (const unsigned char *)mpc_rec_ptr(p.s, S, T) + 16 * (u64)(have ? pos : 0u);
 		// pass 1: stored entries of the row (a block's second entry is real unless it repeats the first column or is the
 		// empty-row sentinel; a block's first entry is real unless the row is empty)
 		u32 cnt = 0;

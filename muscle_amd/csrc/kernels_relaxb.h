@@ -105,6 +105,13 @@ struct MpcRbWinCxx {
 typedef MpcRbWinCxx MpcRbWinAsm;
 #endif
 
+// A store in SEGMENTS (StoreParams::pad_zbase): the same merge statement B, and a staging that takes the base address of step Z's
+// records from the per-Z tables instead of `pad` / `win`. A type of its own, so that a store of one segment launches the
+// instantiations it always did, instruction for instruction.
+template <class B> struct MpcRbSegmented : B {};
+template <class B> struct MpcRbIsSegmented { static constexpr bool value = false; };
+template <class B> struct MpcRbIsSegmented<MpcRbSegmented<B> > { static constexpr bool value = true; };
+
 // Wave scans of the walk kernel's prologue through ds_bpermute with the lane number passed in: the caller passes a lane number
 // that went through MPC_OPAQUE inside the tile loop — __shfl_up's own lane number (and the byte index made of it) is a loop
 // invariant the compiler keeps in two VGPRs across the walk.
@@ -521,6 +528,7 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_band_kerne
 	const u32 n = s.n;
 	constexpr u32 NWAVES = THREADS / 64;
 	constexpr bool WIN = BLOCKS::WINDOW;      // the Y records are window records, looked up by column (MpcRbWinAsm / MpcRbWinCxx)
+	constexpr bool SEG = MpcRbIsSegmented<BLOCKS>::value; // the records lie in segments: a base address per step
 	constexpr u32 YREGS = (MAXSLOTS + 5) / 6; // 4 * iy of a slot's cell: 5 bits, 6 slots per register
 	const u32 wave = mpc_wave_first(tid >> 6); // scalar
 	u32 *ptab = (u32 *)(smem_raw + MPC_RB_PTAB); // [64][4]: first cell, cells, pair, first entry
@@ -802,12 +810,26 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_band_kerne
 			*bias = (O + R - Oa + rt_d) << 4;
 			return ftot + mpc_read_lane(incl, 15u);
 		};
-		auto issue_dma = [&](u32 at) { // at: byte offset of the step's buffer in the staging area
+		// A store in segments: table words are relative to the segment of step Zs, whose address is wave-uniform — two scalar loads
+		// from the per-Z table, through the kernarg segment (neither the table's pointer nor the base lives in registers across the
+		// merges: the base is consumed by the transfers issued right here).
+		auto seg_base = [&](const u64 *zbase, u32 Zs) -> const unsigned char * {
+			mpc_const_u32p w = MPC_CONST_U32(zbase + Zs);
+			return (const unsigned char *)((u64)w[0] | ((u64)w[1] << 32));
+		};
+		auto issue_dma = [&](u32 at, u32 Zs) { // at: byte offset of the step's buffer in the staging area; Zs: the step
 			u32 ln = lane;
 			MPC_OPAQUE(ln);
+			const unsigned char *src_pad = padb, *src_win = (const unsigned char *)s.win;
+			if constexpr (SEG) {
+				const auto ps = MPC_KERNARG_AGAIN(p);
+				// (the two copies are cut independently: either may still be one allocation)
+				if (ps->s.pad_zbase) src_pad = seg_base(ps->s.pad_zbase, Zs);
+				if (WIN && ps->s.win_zbase) src_win = seg_base(ps->s.win_zbase, Zs);
+			} else (void)Zs;
 #pragma unroll
 			for (u32 j = 0; j < PIECES; ++j) {
-				const unsigned char *src = (WIN && ((wave + j * NWAVES) & 15u) >= MPC_RB_MAXN) ? (const unsigned char *)s.win : padb;
+				const unsigned char *src = (WIN && ((wave + j * NWAVES) & 15u) >= MPC_RB_MAXN) ? src_win : src_pad;
 				for (u32 c0 = 0; c0 < s_len[j]; c0 += 64u)
 					if (c0 + ln < s_len[j]) mpc_dma16(src + 16 * (u64)(s_src[j] + c0 + ln), stage + at + 16 * (s_dst[j] + c0));
 			}
@@ -828,7 +850,7 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_band_kerne
 			u32 b;
 			cur_len = 16u * step_vectors(0, &b);
 			put_bias(0, y_abs(b, 0u));
-			issue_dma(0);
+			issue_dma(0, 0u);
 			mpc_dma_wait();
 		}
 		constexpr bool STAGING = DIAG < 2 || DIAG == 4; // DIAG 2, 3: step 0's records for every step
@@ -843,7 +865,7 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_band_kerne
 			if (cur_at == 0u) { nxt_at = p.cap_bytes - nxt_len; pre = nxt_len <= p.cap_bytes && nxt_at >= cur_len; }
 			else { nxt_at = 0u; pre = nxt_len <= cur_at; }
 			put_bias(Z + 1, y_abs(b, pre ? nxt_at : 0u)); // (a step that is not prefetched is staged at the bottom, below)
-			if (pre) issue_dma(nxt_at);
+			if (pre) issue_dma(nxt_at, Z + 1);
 #ifdef MPC_RELAX_DIAG_BUILD
 			if (tid == 0) atomicAdd(&p.tile_next[pre ? 9 : 8], 1u); // measurement build: steps prefetched / staged late
 #endif
@@ -907,7 +929,7 @@ __global__ void __launch_bounds__(THREADS, WGS * THREADS / 256) relax_band_kerne
 					u32 b;
 					nxt_len = 16u * step_vectors(Z + 1, &b);
 					nxt_at = 0u;
-					issue_dma(0u);
+					issue_dma(0u, Z + 1);
 				}
 				unsigned long long tw = 0;
 				if (DIAG == 4) tw = mpc_clock();

@@ -92,6 +92,17 @@ struct StoreParams {
 	// PARTIAL STORE (mpcgpu_store_import_part): need[A] != 0 where the records (A, Z) of sequence A exist — a rank whose pairs touch
 	// only the sequences of its blocks builds, reads and commits the records of those sequences only. null: every sequence.
 	const u8 *need;
+	// SEGMENTS (a store whose block or window records pass 2^32 blocks; all four null: `pad` / `win` are one allocation each). The
+	// records are Z-major and every step of a relax reads records of one Z only, so the store is cut into runs of whole Z SLABS (the n
+	// records (., Z)), every run a device allocation of its own, below 2^32 blocks. rec_off / ovf_off (wrec_off / wv_off) are block
+	// indices relative to the segment the record lies in — differences of them mean what they meant —, and
+	//   pad_zbase[Z] (win_zbase[Z]) = address of the segment that holds slab Z (`pad` / `win` are null then: mpc_rec_ptr / mpc_wrec_ptr
+	//   are the one way from a record to its address);
+	//   pad_zend[Z] (win_zend[Z]) = block, relative to that segment, at which slab Z ends: the END of record (n - 1, Z). Entry
+	//   rec_off[Z * n + n] is the first record of slab Z + 1, which starts at 0 where a new segment does: a record's end is
+	//   mpc_rec_end / mpc_wrec_end, never "the next entry".
+	const u64 *pad_zbase, *win_zbase;
+	const u32 *pad_zend, *win_zend;
 };
 
 #define MPC_PAD_ROW 2 // entries per block (16 bytes = one ds_read_b128)
@@ -123,6 +134,21 @@ __device__ __forceinline__ bool mpc_need(const StoreParams &s, u32 A) { return s
 
 // index of record (A,Z) in rec_off: Z-major (see StoreParams::pad)
 __device__ __forceinline__ u64 mpc_rec_index(u32 n, u32 A, u32 Z) { return (u64)Z * n + A; }
+// record (A,Z) in block form / in window form: its address and the block (relative to its segment) at which it ends — see
+// StoreParams::pad_zbase. Everything outside relax_band_kernel's staging that turns a record into an address goes through here.
+__device__ __forceinline__ u32 *mpc_rec_ptr(const StoreParams &s, u32 A, u32 Z)
+{
+	u32 *base = s.pad_zbase ? (u32 *)s.pad_zbase[Z] : s.pad;
+	return base + 4 * (u64)s.rec_off[mpc_rec_index(s.n, A, Z)];
+}
+__device__ __forceinline__ u32 *mpc_wrec_ptr(const StoreParams &s, u32 A, u32 Z)
+{
+	u32 *base = s.win_zbase ? (u32 *)s.win_zbase[Z] : s.win;
+	return base + 4 * (u64)s.wrec_off[mpc_rec_index(s.n, A, Z)];
+}
+__device__ __forceinline__ u32 mpc_rec_end(const StoreParams &s, u32 A, u32 Z) { return (s.pad_zend && A + 1u == s.n) ? s.pad_zend[Z] : s.rec_off[mpc_rec_index(s.n, A, Z) + 1]; }
+__device__ __forceinline__ u32 mpc_wrec_end(const StoreParams &s, u32 A, u32 Z) { return (s.win_zend && A + 1u == s.n) ? s.win_zend[Z] : s.wrec_off[mpc_rec_index(s.n, A, Z) + 1]; }
+__device__ __forceinline__ bool mpc_has_win(const StoreParams &s) { return s.win != nullptr || s.win_zbase != nullptr; }
 
 // One 64-thread workgroup per ordered pair (A,Z): row pointers (exclusive scan of the per-row or
 // per-column counts) and entries (row-major copy, or column-major through tperm).
@@ -209,13 +235,14 @@ __global__ void __launch_bounds__(64) var_build_kernel(StoreParams s)
 		const u32 Z = (u32)(b / s.n), A = (u32)(b % s.n); // b == mpc_rec_index(n, A, Z)
 		const u32 LA = s.seq_len[A];
 		if (!mpc_need(s, A)) continue; // (wave-uniform) a partial store: this sequence has no records, no band entries, no positions
-		u32 *rec_out = s.pad + 4 * (u64)s.rec_off[b];
-		const u32 units = s.rec_off[b + 1] - s.rec_off[b];
+		u32 *rec_out = mpc_rec_ptr(s, A, Z);
+		const u32 rec_end = mpc_rec_end(s, A, Z); // (not rec_off[b + 1]: the next record may open a segment)
+		const u32 units = rec_end - s.rec_off[b];
 		for (u32 q = t; q < units; q += 64) { // every block starts as an empty one
 			rec_out[4 * q] = 0u; rec_out[4 * q + 1] = 0u; rec_out[4 * q + 2] = MPC_PAD_SENTINEL; rec_out[4 * q + 3] = MPC_PAD_SENTINEL;
 		}
 		if (A == Z) { // empty matrix: conspairflat.cpp:39-40 skips Z == X and Z == Y
-			if (s.ovf_off) for (u32 q = t; q < s.nb1; q += 64) s.ovf_off[b * s.nb1 + q] = s.rec_off[b + 1];
+			if (s.ovf_off) for (u32 q = t; q < s.nb1; q += 64) s.ovf_off[b * s.nb1 + q] = rec_end;
 			continue;
 		}
 		const bool fwd = A < Z;
@@ -246,7 +273,7 @@ __global__ void __launch_bounds__(64) var_build_kernel(StoreParams s)
 		__syncthreads(); // empty blocks and scans are in place before the entries go in
 		if (s.ovf_off)
 			for (u32 q = t; q < s.nb1; q += 64)
-				s.ovf_off[b * s.nb1 + q] = MPC_RB_HB * q < LA ? s.rec_off[b] + LA + s_ovf[MPC_RB_HB * q] : s.rec_off[b + 1];
+				s.ovf_off[b * s.nb1 + q] = MPC_RB_HB * q < LA ? s.rec_off[b] + LA + s_ovf[MPC_RB_HB * q] : rec_end;
 		const u32 *e = rec + LX + LY;
 		const u32 *rowv = e + 2 * (u64)nnz;
 		const u32 *tperm = rowv + nnz;
@@ -287,7 +314,7 @@ __global__ void __launch_bounds__(64) win_size_kernel(StoreParams s, u32 *sizes,
 		if (A != Z) {
 			// the span of row a of M(A,Z) = last - first + 1 of the stored columns: from the record of (A,Z) in block form (first block
 			// of the row: its first column; the row's last block: its last column) — already built
-			const u32 *rec = s.pad + 4 * (u64)s.rec_off[b];
+			const u32 *rec = mpc_rec_ptr(s, A, Z);
 			for (u32 a = t; a < LA; a += 64) {
 				u32 blk = a;
 				const u32 c_first = rec[4 * blk + 2] & 0xffffu;
@@ -317,11 +344,11 @@ __global__ void __launch_bounds__(64) win_build_kernel(StoreParams s)
 	const u32 t = threadIdx.x;
 	const u64 total = (u64)s.n * s.n;
 	for (u64 b = blockIdx.x; b < total; b += gridDim.x) {
-		const u32 A = (u32)(b % s.n);
+		const u32 Z = (u32)(b / s.n), A = (u32)(b % s.n);
 		const u32 LA = s.seq_len[A];
 		if (!mpc_need(s, A)) continue; // (wave-uniform) a partial store
-		const u32 *rec = s.pad + 4 * (u64)s.rec_off[b];
-		u32 *wrec = s.win + 4 * (u64)s.wrec_off[b];
+		const u32 *rec = mpc_rec_ptr(s, A, Z);
+		u32 *wrec = mpc_wrec_ptr(s, A, Z);
 		const u32 dblocks = (LA + 1u + 3u) / 4u;
 		u32 *desc = wrec, *vals = wrec + 4 * (u64)dblocks;
 		// spans and first columns per row, exclusive scan of span + 1
@@ -353,7 +380,7 @@ __global__ void __launch_bounds__(64) win_build_kernel(StoreParams s)
 		for (u32 q = t; q < 4u * vblocks; q += 64) vals[q] = 0u; // 0.0f everywhere: guards and the gaps inside the windows
 		if (s.wv_off)
 			for (u32 q = t; q < s.nb1; q += 64)
-				s.wv_off[b * s.nb1 + q] = MPC_RB_HB * q < LA ? s.wrec_off[b] + dblocks + s_off[MPC_RB_HB * q] / 4u : s.wrec_off[b + 1] - 1u;
+				s.wv_off[b * s.nb1 + q] = MPC_RB_HB * q < LA ? s.wrec_off[b] + dblocks + s_off[MPC_RB_HB * q] / 4u : mpc_wrec_end(s, A, Z) - 1u;
 		__syncthreads();
 		// the probabilities: every entry of the block-form record goes to off(row) + (col - first col of the row)
 		for (u32 a = t; a < LA; a += 64) {
@@ -384,10 +411,10 @@ __global__ void __launch_bounds__(64) win_pos_kernel(StoreParams s)
 		const u32 *prec = s.packed + s.pbase[k];
 		const u32 *ent = prec + LX + LY;
 		const u32 nnz = (u32)(s.vbase[k + 1] - s.vbase[k]);
-		const u32 *dxy = s.win + 4 * (u64)s.wrec_off[mpc_rec_index(s.n, X, Y)];
-		const u32 *dyx = s.win + 4 * (u64)s.wrec_off[mpc_rec_index(s.n, Y, X)];
 		const bool nx = mpc_need(s, X), ny = mpc_need(s, Y); // (a partial store has the records of the needed sequences only)
 		if (!nx && !ny) continue;
+		const u32 *dxy = mpc_wrec_ptr(s, X, Y);
+		const u32 *dyx = mpc_wrec_ptr(s, Y, X);
 		for (u32 q = t; q < nnz; q += 64) {
 			const u32 col = ent[2 * (u64)q + 1], row = ent[2 * (u64)nnz + q];
 			if (nx) { const u32 wf = dxy[row]; s.pos_wf[s.vbase[k] + q] = (unsigned short)((wf >> 17) + (col - (wf & 0xfffu))); }
@@ -416,8 +443,8 @@ __global__ void __launch_bounds__(64) var_tile_fit_kernel(StoreParams s, const u
 		u32 best = 0;
 		for (u32 Z = t; Z < n; Z += 64) {
 			const u64 bx = mpc_rec_index(n, x0, Z);
-			u32 sum = s.rec_off[bx + nx] - s.rec_off[bx];
-			if (nys) { const u64 by = mpc_rec_index(n, ys, Z); sum += s.rec_off[by + nys] - s.rec_off[by]; }
+			u32 sum = mpc_rec_end(s, x0 + nx - 1u, Z) - s.rec_off[bx];
+			if (nys) { const u64 by = mpc_rec_index(n, ys, Z); sum += mpc_rec_end(s, ys + nys - 1u, Z) - s.rec_off[by]; }
 			best = sum > best ? sum : best;
 		}
 		for (int d = 32; d >= 1; d >>= 1) { const u32 o = __shfl_down(best, d); best = o > best ? o : best; }
@@ -523,9 +550,10 @@ __global__ void __launch_bounds__(64) commit_pairs_kernel(StoreParams s, u64 k0,
 		if (a >= b) continue;
 		const u32 LX = s.seq_len[X], LY = s.seq_len[Y];
 		u32 *ent = s.packed + s.pbase[k] + LX + LY;
-		u32 *rx = s.pad + 4 * (u64)s.rec_off[mpc_rec_index(s.n, X, Y)], *ry = s.pad + 4 * (u64)s.rec_off[mpc_rec_index(s.n, Y, X)];
-		u32 *wx = s.win ? s.win + 4 * ((u64)s.wrec_off[mpc_rec_index(s.n, X, Y)] + (LX + 1u + 3u) / 4u) : nullptr;
-		u32 *wy = s.win ? s.win + 4 * ((u64)s.wrec_off[mpc_rec_index(s.n, Y, X)] + (LY + 1u + 3u) / 4u) : nullptr;
+		u32 *rx = mpc_rec_ptr(s, X, Y), *ry = mpc_rec_ptr(s, Y, X);
+		const bool hw = mpc_has_win(s);
+		u32 *wx = hw ? mpc_wrec_ptr(s, X, Y) + 4 * (u64)((LX + 1u + 3u) / 4u) : nullptr; // the value area: after the descriptor blocks
+		u32 *wy = hw ? mpc_wrec_ptr(s, Y, X) + 4 * (u64)((LY + 1u + 3u) / 4u) : nullptr;
 		for (u64 e = a + t; e < b; e += 64) {
 			const u32 pb = __float_as_uint(s.vnext[e]);
 			if (pk) ent[2 * (e - vb)] = pb;

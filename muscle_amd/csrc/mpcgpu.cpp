@@ -90,6 +90,20 @@ struct HostBuf {
 	template <class T> T *as() const { return (T *)p; }
 };
 
+// A record store in SEGMENTS (kernels_store.h, StoreParams::pad_zbase): runs of whole Z slabs, each an allocation of its own below
+// 2^32 blocks, and the two per-Z tables the kernels find a record with. Empty: the store is one allocation (d_pad / d_win).
+struct SegStore {
+	std::vector<DevBuf> seg;
+	DevBuf zbase, zend; // [Z]: address of slab Z's segment (u64) / block at which the slab ends inside it (u32)
+	size_t cap() const { size_t t = 0; for (const DevBuf &b : seg) t += b.cap; return t; }
+	void release()
+	{
+		for (DevBuf &b : seg) b.release();
+		seg.clear();
+		zbase.release(); zend.release();
+	}
+};
+
 struct TimedSpan { hipEvent_t a, b; int fam; };
 
 } // namespace
@@ -162,6 +176,7 @@ struct mpcgpu_ctx {
 	DevBuf d_rec_off, d_sizes, d_tilefit;
 	u32 var_max_rec_blocks = 0;  // largest record, 16-byte blocks
 	u64 var_total_blocks = 0;
+	SegStore pad_seg, win_seg;   // block / window records of a store beyond 2^32 blocks (build_var_store); d_pad / d_win are empty then
 	std::string store_desc, tiles_desc, relax_kernel_name; // mpcgpu_relax_info
 	bool relax_fallback = false;
 	// tile list of the LDS-tiled relax, cached per pair range (the sparsity pattern is frozen)
@@ -491,6 +506,22 @@ void fill_store_params(mpcgpu_ctx *c, StoreParams &s)
 	s.nrect = (u32)(c->order_rects.size() / 4);
 	s.rects = s.nrect ? c->d_rects.as<u32>() : nullptr;
 	s.need = c->partial ? c->d_need.as<u8>() : nullptr;
+	// a store in segments: the per-Z tables instead of the one base (which is null: nothing reaches such a store past mpc_rec_ptr)
+	const bool pseg = !c->pad_seg.seg.empty(), wseg = c->win_ok && !c->win_seg.seg.empty();
+	s.pad_zbase = pseg ? c->pad_seg.zbase.as<u64>() : nullptr;
+	s.pad_zend = pseg ? c->pad_seg.zend.as<u32>() : nullptr;
+	s.win_zbase = wseg ? c->win_seg.zbase.as<u64>() : nullptr;
+	s.win_zend = wseg ? c->win_seg.zend.as<u32>() : nullptr;
+	if (pseg) s.pad = nullptr;
+	if (wseg) s.win = nullptr;
+}
+
+// the window records and their tables go (the store keeps block records for the Y operand, or is being replaced)
+void release_windows(mpcgpu_ctx *c)
+{
+	c->win_ok = false;
+	c->d_win.release(); c->win_seg.release();
+	c->d_pos_w.release(); c->d_wv_off.release(); c->d_wsum.release(); c->d_wmaxc.release(); c->d_wrec_off.release();
 }
 
 // position of pair (X,Y), X < Y, in the context's pair order (the host twin of mpc_pair_pos, kernels_store.h)
@@ -545,12 +576,12 @@ static int build_slab_store(mpcgpu_ctx *c)
 	c->band_ok = false;
 	c->partial = false; // (the slabs hold every sequence: a partial store that falls back here is a complete one)
 	TimedSpan ts;
-	c->d_pad.release();
+	c->d_pad.release(); c->pad_seg.release();
 	c->d_pos.release();
 	// the band and window tables of a dense-record store that turned out not to tile go with it (nn * nb1 words each: GBs)
-	c->win_ok = false;
 	c->d_ovf_off.release(); c->d_cell_off.release(); c->d_yr.release(); c->d_ovf_sum.release(); c->d_ovf_maxc.release();
-	c->d_win.release(); c->d_pos_w.release(); c->d_wv_off.release(); c->d_wsum.release(); c->d_wmaxc.release(); c->d_wrec_off.release(); c->d_rec_off.release();
+	release_windows(c);
+	c->d_rec_off.release();
 	c->d_btiles.release();
 	{
 		const char *rm = getenv("MPCGPU_RELAX");
@@ -651,6 +682,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->d_bx_n.release(); c->d_by_n.release(); c->d_order_n.release(); c->d_chain_first_n.release(); c->d_chain_cnt_n.release();
 	c->d_rects.release(); c->d_need.release(); c->d_exp_klist.release(); c->d_exp_valbase.release();
 	c->d_tiles2.release();
+	c->pad_seg.release(); release_windows(c);
 	if (c->ev_post) (void)hipEventDestroy(c->ev_post);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
 	(void)hipStreamDestroy(c->stream);
@@ -954,6 +986,21 @@ int mpcgpu_store_info(mpcgpu_ctx *c, uint64_t out[6])
 	u32 held = 0;
 	for (u32 i = 0; i < c->n; ++i) held += (!c->partial || c->need[i]) ? 1u : 0u;
 	out[5] = held;                                                       // sequences whose records the store holds
+	return 0;
+}
+
+int mpcgpu_plan_store_segments(uint32_t n, const uint32_t *sizes, uint64_t limit_blocks, uint32_t max_segs, uint32_t *z_first, uint64_t *blocks,
+	uint32_t *nsegs)
+{
+	if (!sizes || !nsegs || n == 0) return 1;
+	std::vector<u32> zf;
+	std::vector<u64> bl;
+	const u64 limit = (limit_blocks == 0 || limit_blocks > kStoreSegBlocksMax) ? kStoreSegBlocksMax : limit_blocks; // (as the store build clamps its hook)
+	if (!plan_store_segments(n, sizes, limit, zf, bl)) return 3;
+	*nsegs = (uint32_t)bl.size();
+	if (bl.size() > max_segs || !z_first || !blocks) return 2; // the caller's arrays are too small (*nsegs says what they need)
+	for (size_t g = 0; g < bl.size(); ++g) { z_first[g] = zf[g]; blocks[g] = bl[g]; }
+	z_first[bl.size()] = n;
 	return 0;
 }
 

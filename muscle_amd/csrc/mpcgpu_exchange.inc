@@ -254,8 +254,7 @@ int mpcgpu_cons_iter(mpcgpu_ctx *c, uint64_t k0, uint64_t k1)
 			if (r == 2 && c->win_ok) {
 				// no band fits with the Y rows as windows (one wide row can be most of the LDS): the same tiles with the Y rows as block
 				// lists, i.e. the two-list walk; the window records are dropped
-				c->win_ok = false;
-				c->d_win.release(); c->d_pos_w.release(); c->d_wv_off.release(); c->d_wsum.release(); c->d_wmaxc.release(); c->d_wrec_off.release();
+				release_windows(c);
 				{ const size_t at = c->store_desc.find(" + window records"); if (at != std::string::npos) c->store_desc.erase(at); }
 				c->btiles_k0 = c->btiles_k1 = ~0ull;
 				fill_store_params(c, sp);
@@ -264,7 +263,7 @@ int mpcgpu_cons_iter(mpcgpu_ctx *c, uint64_t k0, uint64_t k1)
 			if (r != 2) return r;
 			c->band_ok = false; // this store's rows do not cut into band tiles that fit: whole-record tiles from here on
 		}
-		if (c->var_pairs_ok) return relax_var(c, sp, k0, k1);
+		if (c->var_pairs_ok) return relax_var(c, sp, k0, k1); // (never a store in segments: build_var_store)
 		if (build_slab_store(c)) return 1; // neither: CSR slabs + the gather kernel (same results)
 		fill_store_params(c, sp);
 	}
