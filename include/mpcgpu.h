@@ -348,6 +348,14 @@ int mpcgpu_work_get(mpcgpu_ctx *ctx, uint64_t *dp_cells, uint64_t *relax_entry_z
  * ran as members of chains (consecutive pairs with the same row sequence swept back to back by one wavefront, no systolic
  * fill/drain in between: kernels_fbc.h), and the number of chains. Same cells, same results; MPCGPU_FB_CHAIN=0 turns chains off. */
 int mpcgpu_stage_a_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint64_t *chained_pairs, uint64_t *chains);
+/* How the last stage A ran the pairs whose row sequence is cut into row blocks (769 residues or more: CalcFwdFlat, fwdflat3.cpp:12-153 /
+ * CalcBwdFlat, bwdflat3.cpp:10-184 over blocks of 64 x 7 or 64 x 4 rows): pairs = the row-block pairs that ran cooperatively, the
+ * wavefronts of a workgroup sweeping the blocks of ONE pair as a pipeline (kernels_fbcoop.h) where otherwise one wavefront walks them
+ * one after the other; waves_per_pair = the wavefronts each such pair had. Both 0 when none ran that way. Same cells, same results
+ * (the candidates of a pair reach the finishing kernels in another order, which those do not depend on). MPCGPU_FB_COOP: 0 never
+ * (also when unset, until the rule has been measured on a device), 1 when a launch has fewer row-block pairs than the chip has wave
+ * slots for them, 2..16 that many waves, always (clamped to the waves of a workgroup the chip keeps resident). */
+int mpcgpu_stage_a_coop_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint32_t *waves_per_pair);
 /* Sizes of the current store, for the measurement's lower bounds (bench.py: min_bytes_per_launch): out[0] bytes of the row-indexed
  * block records, out[1] of the window records (0: not built), out[2] of the packed matrices of all pairs, out[3] stored posteriors
  * of all pairs, out[4] of the pairs this context relaxes, out[5] sequences whose records the store holds (all of them unless the

@@ -9,6 +9,7 @@
 #include "../../include/mpcgpu.h"
 #include "kernels_fb.h"
 #include "kernels_fbc.h"
+#include "kernels_fbcoop.h"
 #include "kernels_post.h"
 #include "kernels_store.h"
 #include "kernels_relaxv.h"
@@ -246,6 +247,7 @@ struct mpcgpu_ctx {
 	hipStream_t stream2 = nullptr;
 	hipEvent_t ev_post = nullptr;
 	u64 sa_pairs = 0, sa_chained = 0, sa_chains = 0; // last stage A: pairs, pairs that ran in chains, chains
+	u64 sa_coop_pairs = 0; u32 sa_coop_waves = 0;    // ... row-block pairs that ran on fb_coop_kernel, and its waves per pair
 	double aa_trace_t[5] = {0, 0, 0, 0, 0}; // MPCGPU_TRACE & 4: host seconds of mpcgpu_align_alns' phases
 	u64 aa_trace_n = 0;
 };
@@ -408,6 +410,46 @@ void launch_fb_long(int H, bool mega, const FbParams &p, u32 grid, u32 block, si
 	else if (H == MPC_LONG_H_SMALL) { if (mega) launch_fb<MPC_LONG_H_SMALL, true, true>(p, grid, block, smem, st); else launch_fb<MPC_LONG_H_SMALL, false, true>(p, grid, block, smem, st); }
 	else if (mega) launch_fb<MPC_LONG_H, true, true>(p, grid, block, smem, st);
 	else launch_fb<MPC_LONG_H, false, true>(p, grid, block, smem, st);
+}
+
+// fb_coop_kernel (kernels_fbcoop.h): the row-block sweep with the waves of a workgroup on one pair. smem includes MPC_FB_COOP_LDS_BYTES.
+template <int H, bool MEGA> void launch_fb_coop_t(const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+{
+	auto kern = fb_coop_kernel<H, MEGA>;
+	ensure_dyn_smem((const void *)kern, smem);
+	MPC_LAUNCH(kern, grid, block, smem, st, p);
+}
+
+template <int H, bool MEGA> int occ_fb_coop_t(u32 block, size_t smem)
+{
+	int nb = 0;
+	ensure_dyn_smem((const void *)fb_coop_kernel<H, MEGA>, smem);
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fb_coop_kernel<H, MEGA>, (int)block, smem) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
+	return nb;
+}
+
+// workgroups of `block` threads a CU keeps resident (0: such a workgroup does not fit)
+int occ_fb_coop(int H, bool mega, u32 block, size_t smem)
+{
+	if (H == 1) return mega ? occ_fb_coop_t<1, true>(block, smem) : occ_fb_coop_t<1, false>(block, smem);
+	if (H == MPC_LONG_H_SMALL) return mega ? occ_fb_coop_t<MPC_LONG_H_SMALL, true>(block, smem) : occ_fb_coop_t<MPC_LONG_H_SMALL, false>(block, smem);
+	return mega ? occ_fb_coop_t<MPC_LONG_H, true>(block, smem) : occ_fb_coop_t<MPC_LONG_H, false>(block, smem);
+}
+
+// waves per workgroup the instantiation is compiled for
+u32 fb_coop_wave_limit(int H, bool mega)
+{
+	if (H == 1) return (u32)(mega ? FbCoopBounds<1, true>::threads : FbCoopBounds<1, false>::threads) / 64;
+	if (H == MPC_LONG_H_SMALL) return (u32)(mega ? FbCoopBounds<MPC_LONG_H_SMALL, true>::threads : FbCoopBounds<MPC_LONG_H_SMALL, false>::threads) / 64;
+	return (u32)(mega ? FbCoopBounds<MPC_LONG_H, true>::threads : FbCoopBounds<MPC_LONG_H, false>::threads) / 64;
+}
+
+void launch_fb_coop(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+{
+	if (H == 1) { if (mega) launch_fb_coop_t<1, true>(p, grid, block, smem, st); else launch_fb_coop_t<1, false>(p, grid, block, smem, st); }
+	else if (H == MPC_LONG_H_SMALL) { if (mega) launch_fb_coop_t<MPC_LONG_H_SMALL, true>(p, grid, block, smem, st); else launch_fb_coop_t<MPC_LONG_H_SMALL, false>(p, grid, block, smem, st); }
+	else if (mega) launch_fb_coop_t<MPC_LONG_H, true>(p, grid, block, smem, st);
+	else launch_fb_coop_t<MPC_LONG_H, false>(p, grid, block, smem, st);
 }
 
 int occ_fb_h(int H, bool mega, u32 block, size_t smem)
@@ -1010,6 +1052,14 @@ int mpcgpu_stage_a_info(mpcgpu_ctx *c, uint64_t *pairs, uint64_t *chained_pairs,
 	if (pairs) *pairs = c->sa_pairs;
 	if (chained_pairs) *chained_pairs = c->sa_chained;
 	if (chains) *chains = c->sa_chains;
+	return 0;
+}
+
+int mpcgpu_stage_a_coop_info(mpcgpu_ctx *c, uint64_t *pairs, uint32_t *waves_per_pair)
+{
+	if (!c) return 1;
+	if (pairs) *pairs = c->sa_coop_pairs;
+	if (waves_per_pair) *waves_per_pair = c->sa_coop_pairs ? c->sa_coop_waves : 0;
 	return 0;
 }
 

@@ -77,6 +77,7 @@ struct BatchPrep {
 	std::vector<u32> chain_first, chain_cnt;
 	u32 ccount[MPC_HMAX + 1];   // chains per rows-per-lane bin
 	u32 cvmax[MPC_HMAX + 1];    // longest virtual column axis of a bin's chains
+	u32 coop_pairs = 0, coop_waves = 0; // set by the launch: row-block pairs that went to fb_coop_kernel, and its waves per pair
 };
 
 // Chains: consecutive pairs of the list with the same row sequence (the all-pairs order is full of them), each with
@@ -243,11 +244,15 @@ static int ensure_pair_scratch(mpcgpu_ctx *c, const StageAGeom &g, u64 B)
 }
 
 // ---- forward/backward, row-block pairs: cnt entries of `order` (fp: fill_fb_params)
-static int launch_fb_row_blocks(mpcgpu_ctx *c, const StageAGeom &g, FbParams fp, const u32 *order, u32 cnt, u64 planes_budget)
+// What both row-block kernels need to know of a launch: rows per lane, blocks and forward-plane floats of the longest pair, the line
+// buffer's row length, the memory the planes may take and the workgroups of SA_BLOCK threads a CU keeps resident.
+struct RowBlockPlan { u32 long_h = 0, nbmax = 0, ld = 0, occ = 0; u64 fm_block = 0, fm_stride = 0, fm_budget = 0; };
+static int row_block_plan(mpcgpu_ctx *c, const StageAGeom &g, u32 cnt, u64 planes_budget, RowBlockPlan &rp)
 {
 	const u32 cus = (u32)c->prop.multiProcessorCount;
 	const int long_h_env = env_int("MPCGPU_FB_LONG_H", 0); // 0 = chosen below, 1 / 4 / 7 = forced (1: tests reach several blocks with short sequences)
-	const u32 LXlong = g.LXlong, LYlong = g.LYlong, ld = (LYlong + 2 + 63) & ~63u;
+	const u32 LXlong = g.LXlong, LYlong = g.LYlong;
+	rp.ld = (LYlong + 2 + 63) & ~63u;
 	auto planes = [LXlong, LYlong](u32 h, u32 *nb, u64 *blk) { *nb = (LXlong + 64 * h - 1) / (64 * h); *blk = (u64)(LYlong + 64) * h * 64; return *blk * *nb; };
 	// resident waves are bounded by the forward M planes they keep (LX*LY floats each)
 	size_t freeb = 0, totb = 0;
@@ -255,42 +260,114 @@ static int launch_fb_row_blocks(mpcgpu_ctx *c, const StageAGeom &g, FbParams fp,
 	// (up to 45 % of what is free, counting the plane buffer already owned: 36 MB per 3000 x 3000 pair — with the 16 GB the
 	// other scratch is held to, 444 waves were resident where the chip takes 2048. The buffer stays allocated — hipMalloc and
 	// hipFree of ~100 GB take seconds — and is given back only when the store needs the room: mpcgpu_store_import)
-	const u64 fm_budget = std::min<u64>(planes_budget, (u64)((freeb + c->d_fm.cap) * 0.45));
+	rp.fm_budget = std::min<u64>(planes_budget, (u64)((freeb + c->d_fm.cap) * 0.45));
 	// rows per lane: 7 (217 VGPRs, 2 waves per SIMD), or 4 (166 VGPRs, 3 waves per SIMD; more blocks, more line-buffer
 	// traffic) when the pairs and the memory for their forward planes can keep more than 2 waves per SIMD busy
 	// (100 x L~3000: 517 -> 407 ms; 64 x L~6000, 875 waves fit: 1985 ms with 7 rows, 2190 with 4)
-	u32 long_h = long_h_env == 1 ? 1u : long_h_env == MPC_LONG_H_SMALL ? (u32)MPC_LONG_H_SMALL : (u32)MPC_LONG_H;
-	u32 nbmax = 0;
-	u64 fm_block = 0;
+	rp.long_h = long_h_env == 1 ? 1u : long_h_env == MPC_LONG_H_SMALL ? (u32)MPC_LONG_H_SMALL : (u32)MPC_LONG_H;
 	if (long_h_env == 0) {
-		const u64 stride_small = planes(MPC_LONG_H_SMALL, &nbmax, &fm_block);
-		const u64 waves_small = std::min<u64>(cnt, fm_budget / (stride_small * 4 + 16ull * ld * 4));
-		if (waves_small > (u64)cus * 4 * 2) long_h = MPC_LONG_H_SMALL;
+		const u64 stride_small = planes(MPC_LONG_H_SMALL, &rp.nbmax, &rp.fm_block);
+		const u64 waves_small = std::min<u64>(cnt, rp.fm_budget / (stride_small * 4 + 16ull * rp.ld * 4));
+		if (waves_small > (u64)cus * 4 * 2) rp.long_h = MPC_LONG_H_SMALL;
 	}
-	const u64 fm_stride = planes(long_h, &nbmax, &fm_block);
-	const u64 max_waves = fm_budget / (fm_stride * 4 + 16ull * ld * 4);
+	rp.fm_stride = planes(rp.long_h, &rp.nbmax, &rp.fm_block);
+	rp.occ = (u32)occ_fb_long((int)rp.long_h, g.mega, SA_BLOCK, g.fb_smem);
+	return 0;
+}
+
+// fb_kernel<H, MEGA, LONG>: a wave per pair, its blocks one after the other
+static int launch_fb_row_blocks(mpcgpu_ctx *c, const StageAGeom &g, const RowBlockPlan &rp, FbParams fp, const u32 *order, u32 cnt)
+{
+	const u32 cus = (u32)c->prop.multiProcessorCount;
+	const u32 ld = rp.ld, occ = rp.occ;
+	const u64 max_waves = rp.fm_budget / (rp.fm_stride * 4 + 16ull * ld * 4);
 	if (max_waves < 1)
-		return fail(c, "mpcgpu_calc_posteriors: not enough device memory for the forward plane of a %u x %u pair", LXlong, LYlong);
-	const u32 occ = (u32)occ_fb_long((int)long_h, g.mega, SA_BLOCK, g.fb_smem);
+		return fail(c, "mpcgpu_calc_posteriors: not enough device memory for the forward plane of a %u x %u pair", g.LXlong, g.LYlong);
 	u32 grid = std::min<u32>((cnt + SA_WAVES - 1) / SA_WAVES, cus * occ);
 	grid = (u32)std::max<u64>(std::min<u64>(grid, max_waves / SA_WAVES), 1);
 	const u32 wpb = max_waves < (u64)SA_WAVES ? (u32)max_waves : (u32)SA_WAVES; // fewer waves per workgroup when memory is that tight
-	HIPCHK(c, c->d_fm.ensure((u64)grid * wpb * fm_stride * 4));
+	HIPCHK(c, c->d_fm.ensure((u64)grid * wpb * rp.fm_stride * 4));
 	HIPCHK(c, c->d_bnd.ensure((u64)grid * wpb * 16 * ld * 4));
 	if (trace_on()) {
-		fprintf(stderr, "[mpcgpu] fb row blocks: H=%u pairs=%u blocks<=%u grid=%u x %u waves occ=%u fm=%.1f MB\n", long_h, cnt, nbmax,
-			grid, wpb, occ, (double)grid * wpb * fm_stride * 4 / 1048576.0);
+		fprintf(stderr, "[mpcgpu] fb row blocks: H=%u pairs=%u blocks<=%u grid=%u x %u waves occ=%u fm=%.1f MB\n", rp.long_h, cnt, rp.nbmax,
+			grid, wpb, occ, (double)grid * wpb * rp.fm_stride * 4 / 1048576.0);
 		fflush(stderr);
 	}
 	fp.order = order; fp.count = cnt;
 	fp.queue = c->d_queue.as<u32>() + MPC_HMAX + 1;
-	fp.fm_scratch = c->d_fm.as<float>(); fp.fm_stride = fm_stride; fp.fm_block = fm_block;
+	fp.fm_scratch = c->d_fm.as<float>(); fp.fm_stride = rp.fm_stride; fp.fm_block = rp.fm_block;
 	fp.bnd = c->d_bnd.as<float>(); fp.bnd_stride = 16ull * ld; fp.bnd_ld = ld;
 	TimedSpan sp;
 	if (span_begin(c, 0, &sp)) return 1;
-	launch_fb_long((int)long_h, g.mega, fp, grid, 64 * wpb, g.fb_smem, c->stream);
+	launch_fb_long((int)rp.long_h, g.mega, fp, grid, 64 * wpb, g.fb_smem, c->stream);
 	HIPCHK(c, hipGetLastError());
 	return span_end(c, &sp);
+}
+
+// fb_coop_kernel<H, MEGA> (kernels_fbcoop.h): a workgroup of W waves per pair, the blocks as a pipeline. Forward planes and line
+// buffers (a row of 8 states per block boundary) are per resident WORKGROUP; with less memory than the resident workgroups need, fewer
+// workgroups are launched. One launch of timer family 0, like launch_fb_row_blocks.
+static int launch_fb_row_blocks_coop(mpcgpu_ctx *c, const StageAGeom &g, const RowBlockPlan &rp, FbParams fp, const u32 *order, u32 cnt, u32 W)
+{
+	const u32 cus = (u32)c->prop.multiProcessorCount;
+	const u32 ld = rp.ld;
+	const size_t smem = g.fb_smem + MPC_FB_COOP_LDS_BYTES;
+	const u64 bnd_stride = (u64)rp.nbmax * 8 * ld;
+	const u64 max_wgs = rp.fm_budget / (rp.fm_stride * 4 + bnd_stride * 4);
+	if (max_wgs < 1)
+		return fail(c, "mpcgpu_calc_posteriors: not enough device memory for the forward plane of a %u x %u pair", g.LXlong, g.LYlong);
+	const u32 occ = (u32)std::max(occ_fb_coop((int)rp.long_h, g.mega, 64 * W, smem), 1);
+	const u32 grid = (u32)std::max<u64>(std::min<u64>(std::min<u32>(cnt, cus * occ), max_wgs), 1);
+	HIPCHK(c, c->d_fm.ensure((u64)grid * rp.fm_stride * 4));
+	HIPCHK(c, c->d_bnd.ensure((u64)grid * bnd_stride * 4));
+	if (trace_on()) {
+		fprintf(stderr, "[mpcgpu] fb row blocks: H=%u pairs=%u blocks<=%u grid=%u x %u waves occ=%u fm=%.1f MB\n", rp.long_h, cnt, rp.nbmax,
+			grid, W, occ, (double)grid * rp.fm_stride * 4 / 1048576.0);
+		fprintf(stderr, "[mpcgpu] fb coop: W=%u waves per pair (fb_coop_kernel), line buffers %.1f MB\n", W, (double)grid * bnd_stride * 4 / 1048576.0);
+		fflush(stderr);
+	}
+	fp.order = order; fp.count = cnt;
+	fp.queue = c->d_queue.as<u32>() + MPC_HMAX + 1;
+	fp.fm_scratch = c->d_fm.as<float>(); fp.fm_stride = rp.fm_stride; fp.fm_block = rp.fm_block;
+	fp.bnd = c->d_bnd.as<float>(); fp.bnd_stride = bnd_stride; fp.bnd_ld = ld;
+	TimedSpan sp;
+	if (span_begin(c, 0, &sp)) return 1;
+	launch_fb_coop((int)rp.long_h, g.mega, fp, grid, 64 * W, smem, c->stream);
+	HIPCHK(c, hipGetLastError());
+	return span_end(c, &sp);
+}
+
+// Waves per pair of a row-block launch: 0 = fb_kernel<.., LONG> (a wave per pair), 2.. = fb_coop_kernel with that many.
+// MPCGPU_FB_COOP: 0 = never, 1 = the rule below, 2..16 = that many on every row-block launch, clamped to the waves of a workgroup
+// the CU keeps resident for this instantiation (occ_fb_long: VGPRs) and to what the instantiation is compiled for.
+// The rule: cooperative only when the launch leaves wave slots empty — fewer row-block pairs than the chip has resident waves for them —
+// and the longest pair has at least two blocks; W = min(waves of a workgroup, blocks of the longest pair, resident waves / pairs).
+// UNSET is 0 for now: the rule may choose the cooperative kernel only where it has been MEASURED faster than the single-wave kernel
+// by more than the run-to-run spread, and no device time of a long pair has been recorded yet (DESIGN.md 1a) — the measurement
+// (1 x 12 200^2, 8 x 6 000^2, 100 x 3 000^2, 64 x 6 000^2 with MPCGPU_FB_COOP = 0 / 1 / 2 / 4 / 16) sets kFbCoopDefault to 1 or leaves it.
+static const int kFbCoopDefault = 0;
+static u32 fb_coop_waves(const mpcgpu_ctx *c, const StageAGeom &g, const RowBlockPlan &rp, u32 cnt)
+{
+	const int env = env_int("MPCGPU_FB_COOP", kFbCoopDefault);
+	if (env <= 0) return 0;
+	const u32 wmax = std::min<u32>(std::min<u32>(rp.occ * SA_WAVES, fb_coop_wave_limit((int)rp.long_h, g.mega)), 16u);
+	u32 W;
+	if (env >= 2) W = std::min<u32>((u32)env, wmax);
+	else {
+		const u64 resident = (u64)c->prop.multiProcessorCount * rp.occ * SA_WAVES;
+		if (rp.nbmax < 2 || cnt >= resident) return 0;
+		W = (u32)std::min<u64>(std::min<u32>(wmax, rp.nbmax), resident / cnt);
+	}
+	return W >= 2 ? W : 0;
+}
+
+static int launch_fb_row_block_pairs(mpcgpu_ctx *c, const StageAGeom &g, const FbParams &fp, const u32 *order, u32 cnt, u64 planes_budget, BatchPrep &P)
+{
+	RowBlockPlan rp;
+	if (row_block_plan(c, g, cnt, planes_budget, rp)) return 1;
+	const u32 W = fb_coop_waves(c, g, rp, cnt);
+	P.coop_pairs = W ? cnt : 0; P.coop_waves = W;
+	return W ? launch_fb_row_blocks_coop(c, g, rp, fp, order, cnt, W) : launch_fb_row_blocks(c, g, rp, fp, order, cnt);
 }
 
 // ---- forward/backward, one fb_kernel launch per rows-per-lane bin: `order` lists hcount[1] pairs of bin 1, then hcount[2] of bin 2, ...
@@ -365,7 +442,7 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 }
 
 // The sweeps of a batch: its index arrays go up (the NEXT set while the current batch is on the device), then row blocks, single pairs, chains.
-static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &plan, u64 planes_budget, const BatchPrep &P, bool into_next)
+static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &plan, u64 planes_budget, BatchPrep &P, bool into_next)
 {
 	DevBuf &dbx = into_next ? c->d_bx_n : c->d_bx, &dby = into_next ? c->d_by_n : c->d_by, &dord = into_next ? c->d_order_n : c->d_order;
 	DevBuf &dcf = into_next ? c->d_chain_first_n : c->d_chain_first, &dcc = into_next ? c->d_chain_cnt_n : c->d_chain_cnt;
@@ -378,10 +455,11 @@ static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &
 	HIPCHK(c, c->d_flags.ensure(B * 4));
 	FbParams fp;
 	fill_fb_params(c, fp, dbx.as<u32>(), dby.as<u32>(), g.capc, g.mega);
+	P.coop_pairs = P.coop_waves = 0;
 	if (P.hcount[MPC_HMAX + 1]) { // the order lists the row-block pairs last: bins ascend
 		u32 first = 0;
 		for (u32 H = 1; H <= MPC_HMAX; ++H) first += P.hcount[H];
-		if (launch_fb_row_blocks(c, g, fp, dord.as<u32>() + first, P.hcount[MPC_HMAX + 1], planes_budget)) return 1;
+		if (launch_fb_row_block_pairs(c, g, fp, dord.as<u32>() + first, P.hcount[MPC_HMAX + 1], planes_budget, P)) return 1;
 	}
 	return launch_fb_bins(c, g, fp, dord.as<u32>(), P.hcount, B) || launch_fb_chains(c, g, plan, fp, P, dord.as<u32>(), dcf.as<u32>(), dcc.as<u32>());
 }
@@ -542,6 +620,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	StageAGeom g = stage_a_geom(c, np, px, py);
 	c->work_cells = g.work_cells;
 	c->sa_pairs = np; c->sa_chained = c->sa_chains = 0;
+	c->sa_coop_pairs = 0; c->sa_coop_waves = 0;
 	const u64 hdr = shard_header_bytes(np);
 	if (np == 0) {
 		HIPCHK(c, c->d_shard.ensure(hdr));
@@ -619,6 +698,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 		c->sa_b0 = done; c->sa_B = B; c->sa_capc = g.capc; c->sa_post_rows = post_rows; c->sa_long_min = g.long_min;
 		done += B;
 		for (u32 c2 : cur.chain_cnt) if (c2 >= 2) { c->sa_chains += 1; c->sa_chained += c2; }
+		if (cur.coop_pairs) { c->sa_coop_pairs += cur.coop_pairs; c->sa_coop_waves = cur.coop_waves; }
 		std::swap(cur, nxt);
 		if (cur.valid) { // the next batch's index arrays become the current set
 			std::swap(c->d_bx, c->d_bx_n); std::swap(c->d_by, c->d_by_n); std::swap(c->d_order, c->d_order_n);
