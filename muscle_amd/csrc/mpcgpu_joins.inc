@@ -1,14 +1,37 @@
 // mpcgpu_joins.inc — alignment of alignments on the device store: CalcAlnFlat, BuildPost, AlignAlns, the PProg join and pair lists
 // (part of mpcgpu.cpp's translation unit). Reference: alnalnsflat.cpp:7-52, buildpostflat.cpp:18-106, alnmsasflat.cpp:4-50, alignpairflat.cpp:3-27.
+
+// ---- the dispatchers' limits, each in one place (tests/_joins.py and tests/_align_pairs.py restate them)
+static const size_t MPC_LDS_MAX = 160u * 1024u; // dynamic LDS one workgroup may ask for
+static const u64 MPC_ROWS_PAIRS_MAX = 2048; // row form of BuildPost: ordered pairs n1 * n2 of a join
+static const u64 MPC_ROWS_CELLS1_MAX = 1u << 26; // row form, one join: n1 * C1 entries of the column -> position table
+static const u64 MPC_ROWS_CELLS1_MAX_BATCH = 1u << 22; // the same in a list of joins (why it is smaller: not recorded)
+// the one-wave alignment (calc_aln_wave_kernel and its batch form): LY + 1 columns in a wave's registers, LX + 1 rows of traceback codes in LDS
+static size_t aln_wave_smem(u64 lds_rows) { return (size_t)(lds_rows * MPC_ALNW_ROWBYTES + 16); }
+static bool aln_wave_fits(u32 LX, u32 LY) { return (u64)LY + 1 <= MPC_ALNW_MAXW && aln_wave_smem((u64)LX + 1) <= MPC_LDS_MAX; }
+
+// ---- the result record of an alignment {u32 path length, f32 score, path of at most LX + LY letters}: written by the kernel, read by the host
+static u64 aln_rec_stride(u64 Lsum) { return (8 + Lsum + 7) & ~7ull; } // from one record to the next where several lie together
+static AlnParams aln_params(const float *post, u32 LX, u32 LY, char *tb, char *rev, char *rec) { return {post, LX, LY, tb, rev, rec + 8, (u32 *)rec, (float *)(rec + 4)}; }
+static int aln_rec_read(mpcgpu_ctx *c, const char *who, const char *rec, u32 LX, u32 LY, char *path, u32 *pathlen, float *score)
+{
+	u32 n_path;
+	memcpy(&n_path, rec, 4);
+	if (n_path > LX + LY) return fail(c, "%s: path length %u out of range (internal error)", who, n_path);
+	*pathlen = n_path;
+	if (score) memcpy(score, rec + 4, 4);
+	memcpy(path, rec + 8, n_path);
+	return 0;
+}
+
 // CalcAlnFlat + TraceBackFlat on a dense LX x LY matrix already in device memory
 static int run_calc_aln(mpcgpu_ctx *c, const float *d_post, uint32_t LX, uint32_t LY, char *path, uint32_t *pathlen, float *score)
 {
 	const u64 W = (u64)LY + 1;
 	// one wavefront with the previous row in registers and the traceback codes in LDS when the matrix is small enough
 	// (the progressive joins and refinement rounds of L~400 families are), else the workgroup kernel
-	const size_t smem_wave = (size_t)(LX + 1) * MPC_ALNW_ROWBYTES + 16;
 	const int pick = env_int("MPCGPU_ALN_KERNEL", 0); // 0 = by size, 1 = one wave, 2 = several waves, 3 = LDS rows, 4 = LDS rows in column tiles
-	const bool wave = W <= MPC_ALNW_MAXW && smem_wave <= 160u * 1024u && (pick == 0 || pick == 1);
+	const bool wave = aln_wave_fits(LX, LY) && (pick == 0 || pick == 1);
 	// several waves, 4 columns per thread, previous row in registers: up to 4096 columns
 	const u32 qthreads = (u32)((W + 4 * 64 - 1) / (4 * 64)) * 64;
 	const bool quad = !wave && qthreads <= 1024 && (pick == 0 || pick == 2);
@@ -16,20 +39,15 @@ static int run_calc_aln(mpcgpu_ctx *c, const float *d_post, uint32_t LX, uint32_
 	// two DP rows of LY + 1 floats in LDS; wider than that (or MPCGPU_ALN_KERNEL=4): the same rows in column tiles, the tile's left
 	// edge carried through device memory (calc_aln_tiled_kernel). MPCGPU_ALN_TILE: columns per tile (tests: several tiles of a small matrix)
 	const size_t smem_rows = (size_t)(2 * W + MPC_ALN_THREADS / 64 + 4) * 4;
-	const bool tiled = !wave && !quad && (pick == 4 || smem_rows > 160u * 1024u);
+	const bool tiled = !wave && !quad && (pick == 4 || smem_rows > MPC_LDS_MAX);
 	const u32 tile = tiled ? (u32)std::min<u64>(W, (u64)std::min(std::max(env_int("MPCGPU_ALN_TILE", 16384), 1), 16384)) : 0;
-	const size_t smem = wave ? smem_wave : quad ? (size_t)MPC_ALNQ_HDR + (size_t)qrows * qthreads : tiled ? (size_t)(2 * ((u64)tile + 1) + MPC_ALN_THREADS / 64 + 4) * 4 : smem_rows;
+	const size_t smem = wave ? aln_wave_smem((u64)LX + 1) : quad ? (size_t)MPC_ALNQ_HDR + (size_t)qrows * qthreads : tiled ? (size_t)(2 * ((u64)tile + 1) + MPC_ALN_THREADS / 64 + 4) * 4 : smem_rows;
 	if (tiled) HIPCHK(c, c->d_aln_bnd.ensure_grow(2 * ((u64)LX + 1) * 4));
 	HIPCHK(c, c->d_aln_tb.ensure_grow(((u64)LX + 1) * (quad ? (u64)qthreads : W))); // letters per cell, or one byte per thread and row
 	HIPCHK(c, c->d_aln_rev.ensure_grow((u64)LX + LY));
-	// one result record {path length, score, path}: one copy back, one wait
-	const u64 res_bytes = 8 + (u64)LX + LY;
-	HIPCHK(c, c->h_aln_res.ensure(res_bytes));
-	AlnParams ap;
-	ap.post = d_post; ap.LX = LX; ap.LY = LY;
-	ap.tb = c->d_aln_tb.as<char>(); ap.rev = c->d_aln_rev.as<char>();
+	HIPCHK(c, c->h_aln_res.ensure(8 + (u64)LX + LY)); // one result record, unpadded
 	// the record is written straight into page-locked host memory (device-visible: hipHostMalloc): no copy back, one wait
-	ap.pathlen = c->h_aln_res.as<u32>(); ap.score = c->h_aln_res.as<float>() + 1; ap.path = c->h_aln_res.as<char>() + 8;
+	const AlnParams ap = aln_params(d_post, LX, LY, c->d_aln_tb.as<char>(), c->d_aln_rev.as<char>(), c->h_aln_res.as<char>());
 	const int which = wave ? 0 : quad ? 1 : tiled ? 4 : 2;
 	if (smem > c->aln_smem_set[which]) { // raise the kernel's dynamic-LDS limit only when this call needs more than any before
 		(void)hipFuncSetAttribute(wave ? (const void *)calc_aln_wave_kernel : quad ? (const void *)calc_aln_quad_kernel : tiled ? (const void *)calc_aln_tiled_kernel : (const void *)calc_aln_kernel,
@@ -46,12 +64,7 @@ static int run_calc_aln(mpcgpu_ctx *c, const float *d_post, uint32_t LX, uint32_
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts_aln)) return 1;
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const u32 n_path = c->h_aln_res.as<u32>()[0];
-	if (n_path > LX + LY) return fail(c, "mpcgpu_calc_aln: path length %u out of range (internal error)", n_path);
-	*pathlen = n_path;
-	if (score) memcpy(score, c->h_aln_res.as<char>() + 4, 4);
-	memcpy(path, c->h_aln_res.as<char>() + 8, n_path);
-	return 0;
+	return aln_rec_read(c, "mpcgpu_calc_aln", c->h_aln_res.as<char>(), LX, LY, path, pathlen, score);
 }
 
 // The finishing kernels (kernels_post.h) on ONE caller-supplied list of cells with Score >= MIN_SPARSE_SCORE — what fb_kernel
@@ -164,134 +177,172 @@ static int reduce_runs(mpcgpu_ctx *c, const RunBufs &rb, const u32 *keys_sorted,
 	return 0;
 }
 
-// BuildPost on the device store (+ CalcAlnFlat when path != NULL): the body of mpcgpu_align_alns_w and mpcgpu_build_post (who: the
-// entry point, for the messages about the caller's maps). A row's position -> column map must rise strictly (Sequence::GetPosToCol of
-// an aligned row): two positions on one column would add twice into one cell of the matrix.
-static int build_post_impl(mpcgpu_ctx *c, const char *who, uint32_t n1, const uint32_t *seq1, uint32_t n2, const uint32_t *seq2, uint32_t C1,
-	uint32_t C2, const uint32_t *pos2col1, const uint32_t *pos2col2, const float *w1, const float *w2, char *path,
-	uint32_t *pathlen, float *score)
+// The tail of the general path. The generating kernel left M {cell, value} records in the first halves of d_bp_keys / d_bp_vals: sort them by cell into
+// the second halves (fewer than two: nothing to sort), add every cell's run in order. timed: under the spans of families 6 and 7 (build_post_impl's).
+static int sort_reduce(mpcgpu_ctx *c, const RunBufs &rb, u64 M, u64 cells, bool timed)
 {
-	if (!c) return 1;
+	u32 *keys_in = c->d_bp_keys.as<u32>(), *keys_out = keys_in + std::max<u64>(M, 1);
+	float *vals_in = c->d_bp_vals.as<float>(), *vals_out = vals_in + std::max<u64>(M, 1);
+	TimedSpan ts;
+	if (timed && span_begin(c, 6, &ts)) return 1;
+	if (M > 1)
+		HIPCHK(c, mpc_sort_pairs([&](size_t bytes) -> void * { return c->d_bp_tmp.ensure_grow(bytes) == hipSuccess ? c->d_bp_tmp.p : nullptr; },
+			keys_in, keys_out, vals_in, vals_out, (size_t)M, bits_for(cells - 1), c->stream));
+	if (timed && (span_end(c, &ts) || span_begin(c, 7, &ts))) return 1;
+	if (reduce_runs(c, rb, M > 1 ? keys_out : keys_in, M > 1 ? vals_out : vals_in, M, cells)) return 1;
+	return timed ? span_end(c, &ts) : 0;
+}
+
+// One join as its entry point received it: MSA1's and MSA2's rows (sequence indices), their position -> column maps one after the other,
+// weights (NULL: none, or all 1.0f). len1, len2: residues of each side, the length of its maps.
+struct JoinIn { u32 n1, n2, C1, C2; const u32 *seq1, *seq2, *map1, *map2; const float *w1, *w2; u64 len1, len2; };
+// the row form of BuildPost (build_post_rows_kernel) takes it: needs the variable-size record store (every ordered pair by row)
+static bool rows_form_fits(const mpcgpu_ctx *c, const JoinIn &j, u64 pairs_max, bool batch)
+{
+	return c->have_pad && (u64)j.n1 * j.n2 <= pairs_max && j.C2 <= 1024u && (u64)j.n1 * j.C1 <= (batch ? MPC_ROWS_CELLS1_MAX_BATCH : MPC_ROWS_CELLS1_MAX);
+}
+// two arrays of 4-byte items, one after the other
+static void put_pair(void *dst, const void *a, size_t na, const void *b, size_t nb) { memcpy(dst, a, 4 * na); memcpy((char *)dst + 4 * na, b, 4 * nb); }
+
+// A row's position -> column map lies inside its alignment's C columns and rises strictly (Sequence::GetPosToCol of an aligned row): two
+// positions on one column would add twice into one cell of the matrix. unit: what `row` counts in the message ("row", or "in pair" for
+// mpcgpu_align_msas); sfx: " (join j)" in a list of joins, else empty.
+static int check_row_map(mpcgpu_ctx *c, const char *who, u32 side, const char *unit, u32 row, const u32 *map, u32 L, u32 C, const char *sfx)
+{
+	for (u32 pos = 0; pos < L; ++pos) {
+		if (map[pos] >= C) return fail(c, "%s: column map of MSA%u out of range%s", who, side, sfx);
+		if (pos && map[pos] <= map[pos - 1]) return fail(c, "%s: column map of MSA%u %s %u is not strictly increasing at position %u%s", who, side, unit, row, pos, sfx);
+	}
+	return 0;
+}
+
+// ---- the row form of BuildPost (kernels_prog.h: build_post_rows_kernel): a join's inputs are one slice of a page-locked host record,
+// [seqs: n1+n2 u32][c2p: n1*C1 u32, MSA1's maps inverted][off2: n2+1 u32][maps2: len2 u32][weights: n1+n2 f32, when given]
+static u64 rows_slice_bytes(const JoinIn &j) { return 4 * ((u64)j.n1 + j.n2 + (u64)j.n1 * j.C1 + j.n2 + 1 + j.len2 + (j.w1 ? (u64)j.n1 + j.n2 : 0)); }
+// Validates the join (MSA1's maps, MSA2's maps, no sequence on both sides: before anything of it is launched) and writes its slice at `at` of hin.
+// rp's pointers are formed from base: hin where the kernel reads the page-locked record, or its device copy; rp.post and rp.err are the caller's.
+// join: the index in a list of joins, for the messages; -1: a single join.
+static int stage_rows(mpcgpu_ctx *c, const char *who, int64_t join, const JoinIn &j, char *hin, const char *base, u64 at, BuildPostRowsParams &rp)
+{
+	char sfx[24] = "";
+	if (join >= 0) snprintf(sfx, sizeof sfx, " (join %u)", (u32)join);
+	const u64 o_seqs = at, o_c2p = o_seqs + 4 * ((u64)j.n1 + j.n2), o_off2 = o_c2p + 4 * (u64)j.n1 * j.C1, o_maps2 = o_off2 + 4 * ((u64)j.n2 + 1), o_w = o_maps2 + 4 * j.len2;
+	u32 *seqs = (u32 *)(hin + o_seqs), *c2p = (u32 *)(hin + o_c2p), *off2 = (u32 *)(hin + o_off2), *maps2 = (u32 *)(hin + o_maps2);
+	put_pair(seqs, j.seq1, j.n1, j.seq2, j.n2);
+	for (u64 q = 0; q < (u64)j.n1 * j.C1; ++q) c2p[q] = MPC_BPR_GAP;
+	u64 m = 0;
+	for (u32 a = 0; a < j.n1; ++a) {
+		const u32 L = c->len[j.seq1[a]];
+		if (check_row_map(c, who, 1, "row", a, j.map1 + m, L, j.C1, sfx)) return 1;
+		for (u32 pos = 0; pos < L; ++pos) c2p[(u64)a * j.C1 + j.map1[m + pos]] = pos;
+		m += L;
+	}
+	off2[0] = 0;
+	for (u32 b = 0; b < j.n2; ++b) off2[b + 1] = off2[b] + c->len[j.seq2[b]];
+	memcpy(maps2, j.map2, 4 * (size_t)j.len2);
+	for (u32 b = 0; b < j.n2; ++b)
+		if (check_row_map(c, who, 2, "row", b, maps2 + off2[b], off2[b + 1] - off2[b], j.C2, sfx)) return 1;
+	for (u32 a = 0; a < j.n1; ++a)
+		for (u32 b = 0; b < j.n2; ++b) if (j.seq1[a] == j.seq2[b])
+			return join < 0 ? fail(c, "mpcgpu_align_alns: sequence %u is in both alignments", j.seq1[a]) : fail(c, "%s: sequence %u is in both alignments of join %u", who, j.seq1[a], (u32)join);
+	if (j.w1) put_pair(hin + o_w, j.w1, j.n1, j.w2, j.n2);
+	fill_store_params(c, rp.s);
+	rp.seq1 = (const u32 *)(base + o_seqs); rp.seq2 = rp.seq1 + j.n1; rp.n1 = j.n1; rp.n2 = j.n2; rp.C1 = j.C1; rp.C2 = j.C2;
+	rp.c2p1 = (const u32 *)(base + o_c2p); rp.p2c2 = (const u32 *)(base + o_maps2); rp.off2 = (const u32 *)(base + o_off2);
+	rp.w1 = j.w1 ? (const float *)(base + o_w) : nullptr; rp.w2 = j.w1 ? rp.w1 + j.n1 : nullptr;
+	return 0;
+}
+
+// MPCGPU_TRACE & 4: host wall time of a join's phases (vectors, uploads, launches, calc_aln + syncs), summed per context: the shrub
+// workers of -super7 call build_post_impl concurrently on their own contexts
+struct LapTimer {
+	mpcgpu_ctx *c; bool on = false; double t_prev = 0.0;
+	static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+	void start() { static const bool host_trace = trace_host(); on = host_trace; t_prev = on ? now() : 0.0; }
+	void lap(int k) { if (on) { const double t = now(); c->aa_trace_t[k] += t - t_prev; t_prev = t; } }
+};
+
+// build_post_impl's argument and length checks; starts the lap timer once the device is set, fills in len1 and len2 and drops weights
+// that are all 1.0f (what MPCFlat::Run sets): (1*1)*P == P, skip the multiply
+static int build_post_check(mpcgpu_ctx *c, JoinIn &j, const char *path, const uint32_t *pathlen, LapTimer &lt)
+{
 	if (!c->have_store) return fail(c, "mpcgpu_align_alns: no store (call mpcgpu_build_store / mpcgpu_store_import)");
 	// BuildPost reads the records of any sequence: a partial store (a rank of a block-partitioned run) is completed first — once,
 	// from the packed records, which hold the current values
 	if ((c->partial || c->packed_stale) && mpcgpu_store_complete(c)) return 1;
-	if (!seq1 || !seq2 || !pos2col1 || !pos2col2 || (path && !pathlen)) return fail(c, "mpcgpu_align_alns: NULL argument");
-	if (n1 == 0 || n2 == 0 || C1 == 0 || C2 == 0) return fail(c, "mpcgpu_align_alns: empty alignment");
+	if (!j.seq1 || !j.seq2 || !j.map1 || !j.map2 || (path && !pathlen)) return fail(c, "mpcgpu_align_alns: NULL argument");
+	if (j.n1 == 0 || j.n2 == 0 || j.C1 == 0 || j.C2 == 0) return fail(c, "mpcgpu_align_alns: empty alignment");
 	HIPCHK(c, hipSetDevice(c->device));
-	const u32 n = c->n;
-	static const bool host_trace = trace_host(); // diagnostics: host wall time of this call's phases, summed
-	double *acc_t = c->aa_trace_t; // per context: the shrub workers of -super7 call this concurrently on their own contexts
-	u64 &acc_n = c->aa_trace_n;
-	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	double t_prev = host_trace ? now() : 0.0;
-	auto lap = [&](int k) { if (host_trace) { const double t = now(); acc_t[k] += t - t_prev; t_prev = t; } };
-	// ---- host: everything the kernels need from this call in ONE page-locked record, one copy:
-	// [off: n1+n2+1 u64][coff: n1*n2+1 u64][seqs: n1+n2 u32][maps: len1+len2 u32][weights: n1+n2 f32, when not all 1.0f]
-	u64 len1 = 0, len2 = 0;
-	for (u32 a = 0; a < n1; ++a) {
-		if (seq1[a] >= n) return fail(c, "mpcgpu_align_alns: sequence index %u out of range", seq1[a]);
-		len1 += c->len[seq1[a]];
+	lt.start();
+	j.len1 = j.len2 = 0;
+	for (u32 a = 0; a < j.n1 + j.n2; ++a) {
+		const u32 S = a < j.n1 ? j.seq1[a] : j.seq2[a - j.n1];
+		if (S >= c->n) return fail(c, "mpcgpu_align_alns: sequence index %u out of range", S);
+		(a < j.n1 ? j.len1 : j.len2) += c->len[S];
 	}
-	for (u32 b = 0; b < n2; ++b) {
-		if (seq2[b] >= n) return fail(c, "mpcgpu_align_alns: sequence index %u out of range", seq2[b]);
-		len2 += c->len[seq2[b]];
-	}
-	if ((w1 != nullptr) != (w2 != nullptr)) return fail(c, "mpcgpu_align_alns_w: give both weight arrays or neither");
-	bool weighted = false; // all 1.0f (what MPCFlat::Run sets): (1*1)*P == P, skip the multiply
-	if (w1) {
-		for (u32 a = 0; a < n1; ++a) weighted = weighted || w1[a] != 1.0f;
-		for (u32 b = 0; b < n2; ++b) weighted = weighted || w2[b] != 1.0f;
-	}
+	if ((j.w1 != nullptr) != (j.w2 != nullptr)) return fail(c, "mpcgpu_align_alns_w: give both weight arrays or neither");
+	bool weighted = false;
+	for (u32 a = 0; j.w1 && a < j.n1 + j.n2; ++a) weighted = weighted || (a < j.n1 ? j.w1[a] : j.w2[a - j.n1]) != 1.0f;
+	if (!weighted) j.w1 = j.w2 = nullptr;
+	return 0;
+}
+
+// Small joins: the whole matrix in one launch, inputs read from page-locked host memory, and the alignment when path != NULL.
+// MPCGPU_BP: "sort": always the general path; "rows": this one whenever its limits but the pair count allow.
+// 0 = done, 1 = error, 2 = not applicable, or a chunk of pairs overflowed the row kernel's list (very wide posterior rows): the
+// general path does the join
+static int build_post_rows(mpcgpu_ctx *c, const char *who, const JoinIn &j, LapTimer &lt, char *path, uint32_t *pathlen, float *score)
+{
+	const char *bp_mode = getenv("MPCGPU_BP");
+	if (bp_mode && !strcmp(bp_mode, "sort")) return 2;
+	const u64 pairs_max = (bp_mode && !strcmp(bp_mode, "rows")) ? ~0ull : MPC_ROWS_PAIRS_MAX;
+	if (!rows_form_fits(c, j, pairs_max, false)) return 2;
+	const u64 o_err = rows_slice_bytes(j); // the record: the join's slice, then the kernel's overflow flag
+	HIPCHK(c, c->h_bp_in.ensure(o_err + 4));
+	char *hin = c->h_bp_in.as<char>();
+	BuildPostRowsParams rp;
+	if (stage_rows(c, who, -1, j, hin, hin, 0, rp)) return 1;
+	*(u32 *)(hin + o_err) = 0u;
+	lt.lap(0);
+	const u64 cells = (u64)j.C1 * j.C2;
+	HIPCHK(c, c->d_aln_post.ensure_grow(cells * 4));
+	rp.post = c->d_aln_post.as<float>(); rp.err = (u32 *)(hin + o_err);
+	const u32 grid = std::min<u32>(j.C1, (u32)c->prop.multiProcessorCount * 8u);
+	if (trace_on()) { fprintf(stderr, "[mpcgpu] build_post %u x %u rows, %u x %u columns: row kernel, grid %u\n", j.n1, j.n2, j.C1, j.C2, grid); fflush(stderr); }
+	TimedSpan ts_rows;
+	if (span_begin(c, 5, &ts_rows)) return 1;
+	if (j.C2 <= 512u) MPC_LAUNCH(build_post_rows_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
+	else MPC_LAUNCH(build_post_rows_kernel<16>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
+	HIPCHK(c, hipGetLastError());
+	if (span_end(c, &ts_rows)) return 1;
+	lt.lap(2);
+	c->last_post_cells = cells;
+	int rc_rows = 0;
+	if (!path) HIPCHK(c, hipStreamSynchronize(c->stream));
+	else rc_rows = run_calc_aln(c, c->d_aln_post.as<float>(), j.C1, j.C2, path, pathlen, score); // ends with a wait for the stream
+	lt.lap(3);
+	return *(volatile u32 *)(hin + o_err) == 0u ? rc_rows : 2;
+}
+
+// The general path of BuildPost: a record per contribution, sorted by cell, every cell's run added in order. Everything the kernels
+// need from this call in ONE page-locked record, one copy:
+// [off: n1+n2+1 u64][coff: n1*n2+1 u64][seqs: n1+n2 u32][maps: len1+len2 u32][weights: n1+n2 f32, when given]
+static int build_post_general(mpcgpu_ctx *c, const char *who, const JoinIn &j, LapTimer &lt)
+{
+	const u32 n1 = j.n1, n2 = j.n2;
 	const u64 npairs12 = (u64)n1 * n2;
-	// ---- small joins: the whole matrix in one launch, inputs read from page-locked host memory (kernels_prog.h:
-	// build_post_rows_kernel). Needs the variable-size record store (every ordered pair by row).
-	{
-		const char *bp_mode = getenv("MPCGPU_BP"); // "sort": always the general path; "rows": the row kernel whenever its limits allow
-		const bool want_rows = !(bp_mode && !strcmp(bp_mode, "sort"));
-		const u64 pair_limit = (bp_mode && !strcmp(bp_mode, "rows")) ? ~0ull : 2048;
-		if (want_rows && c->have_pad && npairs12 <= pair_limit && C2 <= 1024u && (u64)n1 * C1 <= (1u << 26)) {
-			const u64 r_seqs = 0, r_c2p = r_seqs + 4 * ((u64)n1 + n2), r_off2 = r_c2p + 4 * (u64)n1 * C1, r_maps = r_off2 + 4 * ((u64)n2 + 1),
-				r_w = r_maps + 4 * len2, r_err = r_w + (weighted ? 4 * ((u64)n1 + n2) : 0), r_bytes = r_err + 4;
-			HIPCHK(c, c->h_bp_in.ensure(r_bytes));
-			char *hin = c->h_bp_in.as<char>();
-			u32 *seqs = (u32 *)(hin + r_seqs), *c2p = (u32 *)(hin + r_c2p), *off2 = (u32 *)(hin + r_off2), *maps2 = (u32 *)(hin + r_maps);
-			memcpy(seqs, seq1, 4 * (size_t)n1);
-			memcpy(seqs + n1, seq2, 4 * (size_t)n2);
-			for (u64 q = 0; q < (u64)n1 * C1; ++q) c2p[q] = MPC_BPR_GAP;
-			u64 at = 0;
-			for (u32 a = 0; a < n1; ++a) {
-				const u32 L = c->len[seq1[a]];
-				for (u32 pos = 0; pos < L; ++pos) {
-					const u32 col = pos2col1[at + pos];
-					if (col >= C1) return fail(c, "%s: column map of MSA1 out of range", who);
-					if (pos && col <= pos2col1[at + pos - 1]) return fail(c, "%s: column map of MSA1 row %u is not strictly increasing at position %u", who, a, pos);
-					c2p[(u64)a * C1 + col] = pos;
-				}
-				at += L;
-			}
-			off2[0] = 0;
-			for (u32 b = 0; b < n2; ++b) off2[b + 1] = off2[b] + c->len[seq2[b]];
-			memcpy(maps2, pos2col2, 4 * len2);
-			for (u32 b = 0; b < n2; ++b)
-				for (u32 q = off2[b]; q < off2[b + 1]; ++q) {
-					if (maps2[q] >= C2) return fail(c, "%s: column map of MSA2 out of range", who);
-					if (q > off2[b] && maps2[q] <= maps2[q - 1]) return fail(c, "%s: column map of MSA2 row %u is not strictly increasing at position %u", who, b, q - off2[b]);
-				}
-			for (u32 a = 0; a < n1; ++a)
-				for (u32 b = 0; b < n2; ++b) if (seq1[a] == seq2[b]) return fail(c, "mpcgpu_align_alns: sequence %u is in both alignments", seq1[a]);
-			if (weighted) {
-				float *w = (float *)(hin + r_w);
-				memcpy(w, w1, 4 * (size_t)n1);
-				memcpy(w + n1, w2, 4 * (size_t)n2);
-			}
-			*(u32 *)(hin + r_err) = 0u;
-			lap(0);
-			const u64 cells = (u64)C1 * C2;
-			HIPCHK(c, c->d_aln_post.ensure_grow(cells * 4));
-			BuildPostRowsParams rp;
-			fill_store_params(c, rp.s);
-			rp.seq1 = seqs; rp.seq2 = seqs + n1; rp.n1 = n1; rp.n2 = n2;
-			rp.c2p1 = c2p; rp.p2c2 = maps2; rp.off2 = off2; rp.C1 = C1; rp.C2 = C2;
-			rp.w1 = weighted ? (const float *)(hin + r_w) : nullptr; rp.w2 = weighted ? rp.w1 + n1 : nullptr;
-			rp.post = c->d_aln_post.as<float>(); rp.err = (u32 *)(hin + r_err);
-			const u32 grid = std::min<u32>(C1, (u32)c->prop.multiProcessorCount * 8u);
-			if (trace_on()) { fprintf(stderr, "[mpcgpu] build_post %u x %u rows, %u x %u columns: row kernel, grid %u\n", n1, n2, C1, C2, grid); fflush(stderr); }
-			TimedSpan ts_rows;
-			if (span_begin(c, 5, &ts_rows)) return 1;
-			if (C2 <= 512u) MPC_LAUNCH(build_post_rows_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
-			else MPC_LAUNCH(build_post_rows_kernel<16>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
-			HIPCHK(c, hipGetLastError());
-			if (span_end(c, &ts_rows)) return 1;
-			lap(2);
-			c->last_post_cells = cells;
-			int rc_rows = 0;
-			if (!path) HIPCHK(c, hipStreamSynchronize(c->stream));
-			else rc_rows = run_calc_aln(c, c->d_aln_post.as<float>(), C1, C2, path, pathlen, score); // ends with a wait for the stream
-			lap(3);
-			if (*(volatile u32 *)(hin + r_err) == 0u) return rc_rows;
-			// a chunk of pairs overflowed the row kernel's list (very wide posterior rows): the general path below redoes the join
-		}
-	}
 	const u64 o_off = 0, o_coff = o_off + 8 * ((u64)n1 + n2 + 1), o_seqs = o_coff + 8 * (npairs12 + 1), o_maps = o_seqs + 4 * ((u64)n1 + n2),
-		o_w = o_maps + 4 * (len1 + len2), in_bytes = o_w + (weighted ? 4 * ((u64)n1 + n2) : 0);
+		o_w = o_maps + 4 * (j.len1 + j.len2), in_bytes = o_w + (j.w1 ? 4 * ((u64)n1 + n2) : 0);
 	HIPCHK(c, c->h_bp_in.ensure(in_bytes));
 	char *hin = c->h_bp_in.as<char>();
 	u64 *off = (u64 *)(hin + o_off), *coff = (u64 *)(hin + o_coff);
 	u32 *seqs = (u32 *)(hin + o_seqs), *maps = (u32 *)(hin + o_maps);
-	memcpy(seqs, seq1, 4 * (size_t)n1);
-	memcpy(seqs + n1, seq2, 4 * (size_t)n2);
+	put_pair(seqs, j.seq1, n1, j.seq2, n2);
 	off[0] = 0;
 	for (u32 a = 0; a < n1 + n2; ++a) off[a + 1] = off[a] + c->len[seqs[a]];
-	memcpy(maps, pos2col1, len1 * 4);
-	memcpy(maps + len1, pos2col2, len2 * 4);
-	for (u32 a = 0; a < n1 + n2; ++a) {
-		const u32 C = a < n1 ? C1 : C2, side = a < n1 ? 1 : 2, row = a < n1 ? a : a - n1;
-		for (u64 q = off[a]; q < off[a + 1]; ++q) {
-			if (maps[q] >= C) return fail(c, "%s: column map of MSA%u out of range", who, side);
-			if (q > off[a] && maps[q] <= maps[q - 1]) return fail(c, "%s: column map of MSA%u row %u is not strictly increasing at position %u", who, side, row, (u32)(q - off[a]));
-		}
-	}
+	put_pair(maps, j.map1, j.len1, j.map2, j.len2);
+	for (u32 a = 0; a < n1; ++a) if (check_row_map(c, who, 1, "row", a, maps + off[a], (u32)(off[a + 1] - off[a]), j.C1, "")) return 1;
+	for (u32 b = n1; b < n1 + n2; ++b) if (check_row_map(c, who, 2, "row", b - n1, maps + off[b], (u32)(off[b + 1] - off[b]), j.C2, "")) return 1;
 	coff[0] = 0;
 	for (u32 a = 0; a < n1; ++a)
 		for (u32 b = 0; b < n2; ++b) {
@@ -300,66 +351,60 @@ static int build_post_impl(mpcgpu_ctx *c, const char *who, uint32_t n1, const ui
 			const u64 k = S < T ? pair_pos(c, S, T) : pair_pos(c, T, S); // (position in the context's pair order: all_nnz is kept in it)
 			coff[(u64)a * n2 + b + 1] = coff[(u64)a * n2 + b] + c->all_nnz[k];
 		}
-	if (weighted) {
-		float *w = (float *)(hin + o_w);
-		memcpy(w, w1, 4 * (size_t)n1);
-		memcpy(w + n1, w2, 4 * (size_t)n2);
-	}
+	if (j.w1) put_pair(hin + o_w, j.w1, n1, j.w2, n2);
 	const u64 M = coff[npairs12];
-	const u64 cells = (u64)C1 * C2;
+	const u64 cells = (u64)j.C1 * j.C2;
 	if (cells > 0xffffffffull) return fail(c, "mpcgpu_align_alns: %llu cells exceed this build's cell index", (u64)cells);
-	const u32 bc = bits_for(cells - 1);
 	if (M > 0xffffffffull) return fail(c, "mpcgpu_align_alns: %llu contributions exceed this build's record count", (u64)M);
-	lap(0);
+	lt.lap(0);
 	HIPCHK(c, c->d_bp_in.ensure_grow(in_bytes));
 	HIPCHK(c, hipMemcpyAsync(c->d_bp_in.p, hin, in_bytes, hipMemcpyHostToDevice, c->stream));
-	lap(1);
+	lt.lap(1);
 	HIPCHK(c, c->d_bp_keys.ensure_grow(std::max<u64>(M, 1) * 4 * 2));
 	HIPCHK(c, c->d_bp_vals.ensure_grow(std::max<u64>(M, 1) * 4 * 2));
 	HIPCHK(c, c->d_aln_post.ensure_grow(cells * 4));
 	RunBufs rb;
 	if (prepare_runs(c, M, cells, &rb)) return 1;
-	u32 *keys_in = c->d_bp_keys.as<u32>(), *keys_out = keys_in + std::max<u64>(M, 1);
-	float *vals_in = c->d_bp_vals.as<float>(), *vals_out = vals_in + std::max<u64>(M, 1);
 	const char *din = c->d_bp_in.as<char>();
 	BuildPostParams bp;
 	fill_store_params(c, bp.s);
 	bp.seq1 = (const u32 *)(din + o_seqs); bp.seq2 = bp.seq1 + n1; bp.n1 = n1; bp.n2 = n2;
 	bp.p2c1 = (const u32 *)(din + o_maps); bp.p2c2 = bp.p2c1; // offsets below are into the one concatenated array
 	bp.p2c1_off = (const u64 *)(din + o_off); bp.p2c2_off = bp.p2c1_off + n1;
-	bp.C2 = C2; bp.coff = (const u64 *)(din + o_coff); bp.keys = keys_in; bp.vals = vals_in;
-	bp.w1 = weighted ? (const float *)(din + o_w) : nullptr; bp.w2 = weighted ? bp.w1 + n1 : nullptr;
+	bp.C2 = j.C2; bp.coff = (const u64 *)(din + o_coff); bp.keys = c->d_bp_keys.as<u32>(); bp.vals = c->d_bp_vals.as<float>();
+	bp.w1 = j.w1 ? (const float *)(din + o_w) : nullptr; bp.w2 = j.w1 ? bp.w1 + n1 : nullptr;
 	bp.post = c->d_aln_post.as<float>(); bp.cells = cells; bp.counters = rb.counters;
 	TimedSpan ts_bp;
 	if (span_begin(c, 5, &ts_bp)) return 1;
 	MPC_LAUNCH(build_post_gen_kernel, (u32)std::min<u64>(npairs12, (u64)c->prop.multiProcessorCount * 32), 64, 0, c->stream, bp);
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts_bp)) return 1;
-	const u32 *keys_sorted = keys_in;
-	const float *vals_sorted = vals_in;
-	if (span_begin(c, 6, &ts_bp)) return 1;
-	if (M > 1) {
-		HIPCHK(c, mpc_sort_pairs([&](size_t bytes) -> void * { return c->d_bp_tmp.ensure_grow(bytes) == hipSuccess ? c->d_bp_tmp.p : nullptr; },
-			keys_in, keys_out, vals_in, vals_out, (size_t)M, bc, c->stream));
-		keys_sorted = keys_out;
-		vals_sorted = vals_out;
-	}
-	if (span_end(c, &ts_bp)) return 1;
-	if (span_begin(c, 7, &ts_bp)) return 1;
-	if (reduce_runs(c, rb, keys_sorted, vals_sorted, M, cells)) return 1;
-	if (span_end(c, &ts_bp)) return 1;
-	lap(2);
+	if (sort_reduce(c, rb, M, cells, true)) return 1;
+	lt.lap(2);
 	c->last_post_cells = cells;
-	if (!path) { // matrix only (mpcgpu_build_post); the staging record is reused by the next call: drain the stream
+	return 0;
+}
+
+// BuildPost on the device store (+ CalcAlnFlat when path != NULL): the body of mpcgpu_align_alns_w and mpcgpu_build_post, and of
+// mpcgpu_align_alns_batch for the joins it runs one at a time (who: the entry point, for the messages about the caller's maps)
+static int build_post_impl(mpcgpu_ctx *c, const char *who, JoinIn j, char *path, uint32_t *pathlen, float *score)
+{
+	if (!c) return 1;
+	LapTimer lt{c};
+	if (build_post_check(c, j, path, pathlen, lt)) return 1;
+	const int rc_rows = build_post_rows(c, who, j, lt, path, pathlen, score);
+	if (rc_rows != 2) return rc_rows;
+	if (build_post_general(c, who, j, lt)) return 1;
+	// the staging record is reused by the next call: drain the stream (run_calc_aln ends with a wait for it)
+	if (!path) { // matrix only (mpcgpu_build_post)
 		HIPCHK(c, hipStreamSynchronize(c->stream));
 		return 0;
 	}
-	// the staging record is reused by the next call: run_calc_aln ends with a wait for the stream
-	const int rc_aln = run_calc_aln(c, c->d_aln_post.as<float>(), C1, C2, path, pathlen, score);
-	lap(3);
-	if (host_trace && (++acc_n % 100) == 0)
+	const int rc_aln = run_calc_aln(c, c->d_aln_post.as<float>(), j.C1, j.C2, path, pathlen, score);
+	lt.lap(3);
+	if (lt.on && (++c->aa_trace_n % 100) == 0)
 		fprintf(stderr, "[mpcgpu] align_alns host seconds after %llu calls: vectors %.3f, uploads %.3f, launches %.3f, calc_aln+syncs %.3f\n",
-			(unsigned long long)acc_n, acc_t[0], acc_t[1], acc_t[2], acc_t[3]);
+			(unsigned long long)c->aa_trace_n, c->aa_trace_t[0], c->aa_trace_t[1], c->aa_trace_t[2], c->aa_trace_t[3]);
 	return rc_aln;
 }
 
@@ -369,13 +414,14 @@ int mpcgpu_align_alns_w(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32
 {
 	if (!c) return 1;
 	if (!path || !pathlen) return fail(c, "mpcgpu_align_alns: NULL argument");
-	return build_post_impl(c, "mpcgpu_align_alns", n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, path, pathlen, score);
+	const JoinIn j = {n1, n2, C1, C2, seq1, seq2, pos2col1, pos2col2, w1, w2, 0, 0};
+	return build_post_impl(c, "mpcgpu_align_alns", j, path, pathlen, score);
 }
 
 // calc_aln_wave_batch_kernel, a workgroup of one wave per AlnParams record; lds_rows: the longest LX + 1 among them
 static int launch_aln_wave_batch(mpcgpu_ctx *c, const AlnParams *ap, u32 n, u32 lds_rows)
 {
-	const size_t smem = (size_t)lds_rows * MPC_ALNW_ROWBYTES + 16;
+	const size_t smem = aln_wave_smem(lds_rows);
 	if (smem > c->aln_smem_set[3]) {
 		(void)hipFuncSetAttribute((const void *)calc_aln_wave_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 		c->aln_smem_set[3] = smem;
@@ -392,8 +438,99 @@ static int launch_aln_wave_batch(mpcgpu_ctx *c, const AlnParams *ap, u32 n, u32 
 // alignment: what nearly all joins of a tree are — run TOGETHER: one launch builds every matrix (a workgroup per output row of a join),
 // one launch aligns them (a workgroup per join), one copy in, one wait. 999 joins of a 1000-sequence tree one after the other are 999 x
 // (two one-wave kernels + a round trip): 0.24 s of device time of which almost nothing is arithmetic. A join that does not fit the small
-// forms (the few near the root) is aligned by mpcgpu_align_alns, in list order. Same matrices, same paths: the per-join work is the
+// forms (the few near the root) is aligned by build_post_impl, in list order. Same matrices, same paths: the per-join work is the
 // single-join kernels' body.
+// The plan: every join of the list as a JoinIn (its rows and maps follow the previous join's in seqs and pos2col), and which joins take
+// the batched forms (small). Small implies C2 <= 511 (the one-wave alignment's LY + 1 <= MPC_ALNW_MAXW), so the row kernel's 8 columns
+// per lane always do: there is no <16> batch launch.
+static int plan_joins(mpcgpu_ctx *c, u32 njoins, const u32 *n1, const u32 *n2, const u32 *C1, const u32 *C2, const u32 *seqs, const u32 *pos2col,
+	u32 path_stride, std::vector<JoinIn> &jn, std::vector<u32> &small)
+{
+	for (u32 j = 0; j < njoins; ++j) {
+		JoinIn J = {n1[j], n2[j], C1[j], C2[j], seqs, seqs + n1[j], pos2col, nullptr, nullptr, nullptr, 0, 0};
+		if (J.n1 == 0 || J.n2 == 0 || J.C1 == 0 || J.C2 == 0) return fail(c, "mpcgpu_align_alns_batch: join %u is empty", j);
+		if ((u64)J.C1 + J.C2 > path_stride) return fail(c, "mpcgpu_align_alns_batch: path_stride %u too small for join %u", path_stride, j);
+		for (u32 a = 0; a < J.n1 + J.n2; ++a) {
+			if (seqs[a] >= c->n) return fail(c, "mpcgpu_align_alns_batch: sequence index %u out of range", seqs[a]);
+			(a < J.n1 ? J.len1 : J.len2) += c->len[seqs[a]];
+		}
+		J.map2 = J.map1 + J.len1;
+		seqs += J.n1 + J.n2; pos2col += J.len1 + J.len2;
+		if (rows_form_fits(c, J, MPC_ROWS_PAIRS_MAX, true) && aln_wave_fits(J.C1, J.C2) && njoins > 1) small.push_back(j);
+		jn.push_back(J);
+	}
+	return 0;
+}
+
+// where a join's share of each of a chunk's buffers starts (inputs, output rows, cells, traceback codes, reversed path, result record); the longest C1 + 1 so far
+struct ChunkAt { u64 in = 0, row = 0, cell = 0, tb = 0, rev = 0, res = 0; u32 lds_rows = 0; };
+// A chunk of the small joins js[0..left): as many as keep their matrices within 1 GiB, one join at least. at[q]: where join js[q] starts,
+// at.back(): the totals of the at.size() - 1 joins taken.
+static std::vector<ChunkAt> cut_join_chunk(const std::vector<JoinIn> &jn, const u32 *js, size_t left)
+{
+	std::vector<ChunkAt> at(1);
+	for (size_t q = 0; q < left; ++q) {
+		const JoinIn &j = jn[js[q]];
+		ChunkAt t = at.back();
+		t.in += rows_slice_bytes(j); t.row += j.C1; t.cell += (u64)j.C1 * j.C2; t.tb += ((u64)j.C1 + 1) * ((u64)j.C2 + 1); t.rev += (u64)j.C1 + j.C2;
+		t.res += aln_rec_stride((u64)j.C1 + j.C2); t.lds_rows = std::max(t.lds_rows, j.C1 + 1);
+		if (q && t.cell * 4 > ((u64)1 << 30)) break;
+		at.push_back(t);
+	}
+	return at;
+}
+
+// One chunk of small joins js[0..at.size() - 1): every matrix in one launch, every alignment in the next. A list overflow of the row form
+// (very wide posterior rows) hands nothing out and leaves done[] as it is: the chunk's joins then run one at a time.
+static int run_join_chunk(mpcgpu_ctx *c, const std::vector<JoinIn> &jn, const u32 *js, const std::vector<ChunkAt> &at, u32 path_stride, char *paths,
+	u32 *pathlens, float *scores, unsigned char *done)
+{
+	const ChunkAt &all = at.back();
+	const u32 nb = (u32)at.size() - 1;
+	// one page-locked record, copied to the device once: [rows table][BuildPost parameters][alignment parameters][the joins' inputs]
+	const u64 o_rows = 0, o_bp = (o_rows + 8 * all.row + 15) & ~15ull, o_ap = (o_bp + (u64)nb * sizeof(BuildPostRowsParams) + 15) & ~15ull,
+		o_in = (o_ap + (u64)nb * sizeof(AlnParams) + 15) & ~15ull, o_err = o_in + all.in, total = o_err + 16;
+	HIPCHK(c, c->h_bp_in.ensure(total));
+	HIPCHK(c, c->d_bp_in.ensure_grow(total));
+	HIPCHK(c, c->d_aln_post.ensure_grow(all.cell * 4));
+	HIPCHK(c, c->d_aln_tb.ensure_grow(all.tb));
+	HIPCHK(c, c->d_aln_rev.ensure_grow(all.rev));
+	HIPCHK(c, c->h_aln_res.ensure(all.res));
+	char *hin = c->h_bp_in.as<char>();
+	const char *din = c->d_bp_in.as<char>();
+	u32 *rows = (u32 *)(hin + o_rows);
+	BuildPostRowsParams *bp = (BuildPostRowsParams *)(hin + o_bp);
+	AlnParams *ap = (AlnParams *)(hin + o_ap);
+	for (u32 q = 0; q < nb; ++q) {
+		const JoinIn &j = jn[js[q]];
+		if (stage_rows(c, "mpcgpu_align_alns_batch", js[q], j, hin, din, o_in + at[q].in, bp[q])) return 1;
+		bp[q].post = c->d_aln_post.as<float>() + at[q].cell; bp[q].err = (u32 *)(din + o_err);
+		ap[q] = aln_params(bp[q].post, j.C1, j.C2, c->d_aln_tb.as<char>() + at[q].tb, c->d_aln_rev.as<char>() + at[q].rev, c->h_aln_res.as<char>() + at[q].res);
+		for (u32 col = 0; col < j.C1; ++col) { rows[2 * (at[q].row + col)] = q; rows[2 * (at[q].row + col) + 1] = col; }
+	}
+	memset(hin + o_err, 0, 16);
+	HIPCHK(c, hipMemcpyAsync(c->d_bp_in.p, hin, total, hipMemcpyHostToDevice, c->stream));
+	const u32 grid = (u32)std::min<u64>(all.row, (u64)c->prop.multiProcessorCount * 32u);
+	TimedSpan ts;
+	if (span_begin(c, 5, &ts)) return 1;
+	MPC_LAUNCH(build_post_rows_batch_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)all.row);
+	HIPCHK(c, hipGetLastError());
+	if (span_end(c, &ts)) return 1;
+	if (launch_aln_wave_batch(c, (const AlnParams *)(din + o_ap), nb, all.lds_rows)) return 1;
+	u32 err = 0;
+	HIPCHK(c, hipMemcpyAsync(&err, din + o_err, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	c->last_post_cells = 0;
+	if (err) return 0;
+	for (u32 q = 0; q < nb; ++q) {
+		const u32 j = js[q];
+		if (aln_rec_read(c, "mpcgpu_align_alns_batch", c->h_aln_res.as<char>() + at[q].res, jn[j].C1, jn[j].C2, paths + (u64)j * path_stride, &pathlens[j],
+			scores ? &scores[j] : nullptr)) return 1;
+		done[j] = 1;
+	}
+	return 0;
+}
+
 int mpcgpu_align_alns_batch(mpcgpu_ctx *c, uint32_t njoins, const uint32_t *n1, const uint32_t *n2, const uint32_t *C1, const uint32_t *C2,
 	const uint32_t *seqs, const uint32_t *pos2col, uint32_t path_stride, char *paths, uint32_t *pathlens, float *scores)
 {
@@ -402,154 +539,19 @@ int mpcgpu_align_alns_batch(mpcgpu_ctx *c, uint32_t njoins, const uint32_t *n1, 
 	if (njoins && (!n1 || !n2 || !C1 || !C2 || !seqs || !pos2col || !paths || !pathlens)) return fail(c, "mpcgpu_align_alns_batch: NULL argument");
 	if ((c->partial || c->packed_stale) && mpcgpu_store_complete(c)) return 1;
 	HIPCHK(c, hipSetDevice(c->device));
-	const u32 n = c->n;
-	// where each join's rows and maps start in the caller's arrays; which joins take the batched forms
-	std::vector<u64> soff(njoins + 1, 0), moff(njoins + 1, 0);
+	std::vector<JoinIn> jn;
 	std::vector<u32> small;
-	for (u32 j = 0; j < njoins; ++j) {
-		if (n1[j] == 0 || n2[j] == 0 || C1[j] == 0 || C2[j] == 0) return fail(c, "mpcgpu_align_alns_batch: join %u is empty", j);
-		if ((u64)C1[j] + C2[j] > path_stride) return fail(c, "mpcgpu_align_alns_batch: path_stride %u too small for join %u", path_stride, j);
-		u64 len = 0;
-		for (u32 a = 0; a < n1[j] + n2[j]; ++a) {
-			const u32 S = seqs[soff[j] + a];
-			if (S >= n) return fail(c, "mpcgpu_align_alns_batch: sequence index %u out of range", S);
-			len += c->len[S];
-		}
-		soff[j + 1] = soff[j] + n1[j] + n2[j];
-		moff[j + 1] = moff[j] + len;
-		const bool rows_ok = c->have_pad && (u64)n1[j] * n2[j] <= 2048 && C2[j] <= 1024u && (u64)n1[j] * C1[j] <= (1u << 22);
-		const bool wave_ok = (u64)C2[j] + 1 <= MPC_ALNW_MAXW && (size_t)(C1[j] + 1) * MPC_ALNW_ROWBYTES + 16 <= 160u * 1024u;
-		if (rows_ok && wave_ok && njoins > 1) small.push_back(j);
-	}
+	if (plan_joins(c, njoins, n1, n2, C1, C2, seqs, pos2col, path_stride, jn, small)) return 1;
 	std::vector<unsigned char> done(njoins, 0);
 	// ---- the small joins, in chunks whose matrices fit a budget of device memory
 	for (size_t s0 = 0; s0 < small.size();) {
-		size_t s1 = s0;
-		u64 cells = 0, tbb = 0, revb = 0, inb = 0, nrows = 0, resb = 0;
-		u32 lds_rows = 0;
-		while (s1 < small.size()) {
-			const u32 j = small[s1];
-			const u64 cj = (u64)C1[j] * C2[j];
-			if (s1 > s0 && (cells + cj) * 4 > ((u64)1 << 30)) break;
-			u64 len2 = 0;
-			for (u32 b = 0; b < n2[j]; ++b) len2 += c->len[seqs[soff[j] + n1[j] + b]];
-			cells += cj; tbb += ((u64)C1[j] + 1) * ((u64)C2[j] + 1); revb += (u64)C1[j] + C2[j]; nrows += C1[j];
-			resb += (8 + (u64)C1[j] + C2[j] + 7) & ~7ull;
-			inb += 4 * ((u64)n1[j] + n2[j] + (u64)n1[j] * C1[j] + n2[j] + 1 + len2);
-			lds_rows = std::max(lds_rows, C1[j] + 1);
-			++s1;
-		}
-		const u32 nb = (u32)(s1 - s0);
-		// one page-locked record, copied to the device once: [rows table][BuildPost parameters][alignment parameters][the joins' inputs]
-		const u64 o_rows = 0, o_bp = (o_rows + 8 * nrows + 15) & ~15ull, o_ap = (o_bp + (u64)nb * sizeof(BuildPostRowsParams) + 15) & ~15ull,
-			o_in = (o_ap + (u64)nb * sizeof(AlnParams) + 15) & ~15ull, o_err = o_in + inb, total = o_err + 16;
-		HIPCHK(c, c->h_bp_in.ensure(total));
-		HIPCHK(c, c->d_bp_in.ensure_grow(total));
-		HIPCHK(c, c->d_aln_post.ensure_grow(cells * 4));
-		HIPCHK(c, c->d_aln_tb.ensure_grow(tbb));
-		HIPCHK(c, c->d_aln_rev.ensure_grow(revb));
-		HIPCHK(c, c->h_aln_res.ensure(resb));
-		char *hin = c->h_bp_in.as<char>();
-		const char *din = c->d_bp_in.as<char>();
-		u32 *rows = (u32 *)(hin + o_rows);
-		BuildPostRowsParams *bp = (BuildPostRowsParams *)(hin + o_bp);
-		AlnParams *ap = (AlnParams *)(hin + o_ap);
-		u64 at_in = o_in, at_row = 0, at_cell = 0, at_tb = 0, at_rev = 0, at_res = 0;
-		bool any16 = false, any8 = false;
-		for (u32 q = 0; q < nb; ++q) {
-			const u32 j = small[s0 + q];
-			const u32 *sj = seqs + soff[j], *mj = pos2col + moff[j];
-			u32 *h_seqs = (u32 *)(hin + at_in);
-			const u64 d_seqs = at_in;
-			memcpy(h_seqs, sj, 4 * ((size_t)n1[j] + n2[j]));
-			at_in += 4 * ((u64)n1[j] + n2[j]);
-			u32 *c2p = (u32 *)(hin + at_in);
-			const u64 d_c2p = at_in;
-			at_in += 4 * (u64)n1[j] * C1[j];
-			for (u64 e = 0; e < (u64)n1[j] * C1[j]; ++e) c2p[e] = MPC_BPR_GAP;
-			u64 m = 0;
-			for (u32 a = 0; a < n1[j]; ++a) {
-				const u32 L = c->len[sj[a]];
-				for (u32 pos = 0; pos < L; ++pos) {
-					const u32 col = mj[m + pos];
-					if (col >= C1[j]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA1 out of range (join %u)", j);
-					if (pos && col <= mj[m + pos - 1]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA1 row %u is not strictly increasing at position %u (join %u)", a, pos, j);
-					c2p[(u64)a * C1[j] + col] = pos;
-				}
-				m += L;
-			}
-			u32 *off2 = (u32 *)(hin + at_in);
-			const u64 d_off2 = at_in;
-			at_in += 4 * ((u64)n2[j] + 1);
-			off2[0] = 0;
-			for (u32 b = 0; b < n2[j]; ++b) off2[b + 1] = off2[b] + c->len[sj[n1[j] + b]];
-			u32 *maps2 = (u32 *)(hin + at_in);
-			const u64 d_maps2 = at_in;
-			memcpy(maps2, mj + m, 4 * (size_t)off2[n2[j]]);
-			at_in += 4 * (u64)off2[n2[j]];
-			for (u32 b = 0; b < n2[j]; ++b)
-				for (u32 e = off2[b]; e < off2[b + 1]; ++e) {
-					if (maps2[e] >= C2[j]) return fail(c, "mpcgpu_align_alns_batch: column map of MSA2 out of range (join %u)", j);
-					if (e > off2[b] && maps2[e] <= maps2[e - 1])
-						return fail(c, "mpcgpu_align_alns_batch: column map of MSA2 row %u is not strictly increasing at position %u (join %u)", b, e - off2[b], j);
-				}
-			for (u32 a = 0; a < n1[j]; ++a)
-				for (u32 b = 0; b < n2[j]; ++b) if (sj[a] == sj[n1[j] + b]) return fail(c, "mpcgpu_align_alns_batch: sequence %u is in both alignments of join %u", sj[a], j);
-			BuildPostRowsParams &r = bp[q];
-			fill_store_params(c, r.s);
-			r.seq1 = (const u32 *)(din + d_seqs); r.seq2 = r.seq1 + n1[j]; r.n1 = n1[j]; r.n2 = n2[j];
-			r.c2p1 = (const u32 *)(din + d_c2p); r.p2c2 = (const u32 *)(din + d_maps2); r.off2 = (const u32 *)(din + d_off2);
-			r.C1 = C1[j]; r.C2 = C2[j]; r.w1 = nullptr; r.w2 = nullptr;
-			r.post = c->d_aln_post.as<float>() + at_cell; r.err = (u32 *)(din + o_err);
-			AlnParams &a = ap[q];
-			a.post = r.post; a.LX = C1[j]; a.LY = C2[j];
-			a.tb = c->d_aln_tb.as<char>() + at_tb; a.rev = c->d_aln_rev.as<char>() + at_rev;
-			a.pathlen = (u32 *)(c->h_aln_res.as<char>() + at_res); a.score = (float *)(c->h_aln_res.as<char>() + at_res + 4); a.path = c->h_aln_res.as<char>() + at_res + 8;
-			for (u32 col = 0; col < C1[j]; ++col) { rows[2 * (at_row + col)] = q; rows[2 * (at_row + col) + 1] = col; }
-			at_row += C1[j]; at_cell += (u64)C1[j] * C2[j]; at_tb += ((u64)C1[j] + 1) * ((u64)C2[j] + 1); at_rev += (u64)C1[j] + C2[j];
-			at_res += (8 + (u64)C1[j] + C2[j] + 7) & ~7ull;
-			(C2[j] > 512u ? any16 : any8) = true;
-		}
-		memset(hin + o_err, 0, 16);
-		HIPCHK(c, hipMemcpyAsync(c->d_bp_in.p, hin, total, hipMemcpyHostToDevice, c->stream));
-		const u32 grid = (u32)std::min<u64>(nrows, (u64)c->prop.multiProcessorCount * 32u);
-		TimedSpan ts;
-		if (span_begin(c, 5, &ts)) return 1;
-		if (any8) MPC_LAUNCH(build_post_rows_batch_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)nrows);
-		if (any16) MPC_LAUNCH(build_post_rows_batch_kernel<16>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)nrows);
-		HIPCHK(c, hipGetLastError());
-		if (span_end(c, &ts)) return 1;
-		if (launch_aln_wave_batch(c, (const AlnParams *)(din + o_ap), nb, lds_rows)) return 1;
-		u32 err = 0;
-		HIPCHK(c, hipMemcpyAsync(&err, din + o_err, 4, hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		if (!err) { // (a list overflow of the row form — very wide posterior rows — leaves the chunk to the single-join path below)
-			u64 r_at = 0;
-			for (u32 q = 0; q < nb; ++q) {
-				const u32 j = small[s0 + q];
-				const char *res = c->h_aln_res.as<char>() + r_at;
-				u32 np;
-				memcpy(&np, res, 4);
-				if (np > C1[j] + C2[j]) return fail(c, "mpcgpu_align_alns_batch: path length %u out of range (internal error)", np);
-				pathlens[j] = np;
-				if (scores) memcpy(&scores[j], res + 4, 4);
-				memcpy(paths + (u64)j * path_stride, res + 8, np);
-				done[j] = 1;
-				r_at += (8 + (u64)C1[j] + C2[j] + 7) & ~7ull;
-			}
-		}
-		c->last_post_cells = 0;
-		s0 = s1;
+		const std::vector<ChunkAt> at = cut_join_chunk(jn, small.data() + s0, small.size() - s0);
+		if (run_join_chunk(c, jn, small.data() + s0, at, path_stride, paths, pathlens, scores, done.data())) return 1;
+		s0 += at.size() - 1;
 	}
 	// ---- the others, one after the other
-	for (u32 j = 0; j < njoins; ++j) {
-		if (done[j]) continue;
-		const u32 *sj = seqs + soff[j], *mj = pos2col + moff[j];
-		u64 len1 = 0;
-		for (u32 a = 0; a < n1[j]; ++a) len1 += c->len[sj[a]];
-		if (build_post_impl(c, "mpcgpu_align_alns_batch", n1[j], sj, n2[j], sj + n1[j], C1[j], C2[j], mj, mj + len1, nullptr, nullptr, paths + (u64)j * path_stride, &pathlens[j],
-			scores ? &scores[j] : nullptr)) return 1;
-	}
+	for (u32 j = 0; j < njoins; ++j)
+		if (!done[j] && build_post_impl(c, "mpcgpu_align_alns_batch", jn[j], paths + (u64)j * path_stride, &pathlens[j], scores ? &scores[j] : nullptr)) return 1;
 	return 0;
 }
 
@@ -558,7 +560,8 @@ int mpcgpu_build_post(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32_t
 {
 	if (!c) return 1;
 	if (!post) return fail(c, "mpcgpu_build_post: NULL argument");
-	if (build_post_impl(c, "mpcgpu_build_post", n1, seq1, n2, seq2, C1, C2, pos2col1, pos2col2, w1, w2, nullptr, nullptr, nullptr)) return 1;
+	const JoinIn j = {n1, n2, C1, C2, seq1, seq2, pos2col1, pos2col2, w1, w2, 0, 0};
+	if (build_post_impl(c, "mpcgpu_build_post", j, nullptr, nullptr, nullptr)) return 1;
 	return mpcgpu_get_last_post(c, C1, C2, post);
 }
 
@@ -595,21 +598,12 @@ int mpcgpu_align_msas(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, cons
 		coff[q + 1] = coff[q] + c->sh_nnz[q];
 		rbase[q + 1] = rbase[q] + rec_words(c->len[seq1[q]], c->len[seq2[q]], c->sh_nnz[q]);
 	}
-	// (a row's map must rise strictly, as in build_post_impl)
-	for (u32 q = 0; q < npairs; ++q) {
-		for (u64 x = off1[q]; x < off1[q + 1]; ++x) {
-			if (pos2col1[x] >= C1) return fail(c, "mpcgpu_align_msas: column map of MSA1 out of range");
-			if (x > off1[q] && pos2col1[x] <= pos2col1[x - 1]) return fail(c, "mpcgpu_align_msas: column map of MSA1 in pair %u is not strictly increasing at position %u", q, (u32)(x - off1[q]));
-		}
-		for (u64 x = off2[q]; x < off2[q + 1]; ++x) {
-			if (pos2col2[x] >= C2) return fail(c, "mpcgpu_align_msas: column map of MSA2 out of range");
-			if (x > off2[q] && pos2col2[x] <= pos2col2[x - 1]) return fail(c, "mpcgpu_align_msas: column map of MSA2 in pair %u is not strictly increasing at position %u", q, (u32)(x - off2[q]));
-		}
-	}
+	for (u32 q = 0; q < npairs; ++q) // (a row's map must rise strictly, as in build_post_impl)
+		if (check_row_map(c, "mpcgpu_align_msas", 1, "in pair", q, pos2col1 + off1[q], c->len[seq1[q]], C1, "")
+			|| check_row_map(c, "mpcgpu_align_msas", 2, "in pair", q, pos2col2 + off2[q], c->len[seq2[q]], C2, "")) return 1;
 	const u64 M = coff[npairs];
 	const u64 cells = (u64)C1 * C2;
 	if (cells > 0xffffffffull) return fail(c, "mpcgpu_align_msas: %llu cells exceed this build's cell index", (u64)cells);
-	const u32 bc = bits_for(cells - 1);
 	if (M > 0xffffffffull) return fail(c, "mpcgpu_align_msas: %llu contributions exceed this build's record count", (u64)M);
 	std::vector<u32> maps(off1[npairs] + off2[npairs]);
 	memcpy(maps.data(), pos2col1, off1[npairs] * 4);
@@ -627,8 +621,6 @@ int mpcgpu_align_msas(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, cons
 	HIPCHK(c, c->d_aln_post.ensure(cells * 4));
 	RunBufs rb;
 	if (prepare_runs(c, M, cells, &rb)) return 1;
-	u32 *keys_in = c->d_bp_keys.as<u32>(), *keys_out = keys_in + std::max<u64>(M, 1);
-	float *vals_in = c->d_bp_vals.as<float>(), *vals_out = vals_in + std::max<u64>(M, 1);
 	BuildPostListParams lp;
 	lp.seq_len = c->d_seq_len.as<u32>();
 	lp.packed = c->d_shard.as<u32>();
@@ -637,51 +629,31 @@ int mpcgpu_align_msas(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, cons
 	lp.off1 = c->d_bp_off.as<u64>(); lp.off2 = lp.off1 + (npairs + 1);
 	lp.coff = c->d_bp_coff.as<u64>(); lp.rbase = lp.coff + (npairs + 1);
 	lp.nnz = nullptr; // counts come from coff
-	lp.C2 = C2; lp.keys = keys_in; lp.vals = vals_in;
+	lp.C2 = C2; lp.keys = c->d_bp_keys.as<u32>(); lp.vals = c->d_bp_vals.as<float>();
 	lp.post = c->d_aln_post.as<float>(); lp.cells = cells; lp.counters = rb.counters;
 	MPC_LAUNCH(build_post_list_gen_kernel, (u32)std::min<u64>(npairs, (u64)c->prop.multiProcessorCount * 32), 64, 0, c->stream, lp);
 	HIPCHK(c, hipGetLastError());
-	const u32 *keys_sorted = keys_in;
-	const float *vals_sorted = vals_in;
-	if (M > 1) {
-		HIPCHK(c, mpc_sort_pairs([&](size_t bytes) -> void * { return c->d_bp_tmp.ensure_grow(bytes) == hipSuccess ? c->d_bp_tmp.p : nullptr; },
-			keys_in, keys_out, vals_in, vals_out, (size_t)M, bc, c->stream));
-		keys_sorted = keys_out;
-		vals_sorted = vals_out;
-	}
-	if (reduce_runs(c, rb, keys_sorted, vals_sorted, M, cells)) return 1;
+	if (sort_reduce(c, rb, M, cells, false)) return 1;
 	c->last_post_cells = cells;
 	return run_calc_aln(c, c->d_aln_post.as<float>(), C1, C2, path, pathlen, score); // syncs before the vectors above die
 }
 
 // The one-wave alignments of n pairs (sx[q], sy[q]), their dense matrices at off[q] of c->d_aln_post, in ONE launch: parameters in (ap) and a
-// record {length, score, path} per pair out (res, aln_rec_stride() apart) through page-locked memory that the device addresses; one wait.
+// record {length, score, path} per pair out (res, aln_rec_stride(Lsum_max) apart) through page-locked memory that the device addresses; one wait.
 // ovf: candidate-overflow flags that the same wait brings back (the short list; else NULL): one of them set = 2, nothing handed out.
-static u64 aln_rec_stride(u32 Lsum_max) { return ((u64)8 + Lsum_max + 7) & ~7ull; }
 static int align_wave_batch(mpcgpu_ctx *c, u32 n, const u32 *sx, const u32 *sy, const u64 *off, u32 LXmax, u32 Lsum_max, AlnParams *ap, char *res, const u32 *ovf, u32 path_stride, char *paths, u32 *pathlens, float *scores, float *ea)
 {
 	const u64 rstride = aln_rec_stride(Lsum_max);
-	for (u32 q = 0; q < n; ++q) {
-		char *r = res + (u64)q * rstride;
-		ap[q].post = c->d_aln_post.as<float>() + off[q];
-		ap[q].LX = c->len[sx[q]]; ap[q].LY = c->len[sy[q]];
-		ap[q].tb = nullptr; ap[q].rev = c->d_aln_rev.as<char>() + (u64)q * Lsum_max;
-		ap[q].pathlen = (u32 *)r; ap[q].score = (float *)(r + 4); ap[q].path = r + 8;
-	}
+	for (u32 q = 0; q < n; ++q)
+		ap[q] = aln_params(c->d_aln_post.as<float>() + off[q], c->len[sx[q]], c->len[sy[q]], nullptr, c->d_aln_rev.as<char>() + (u64)q * Lsum_max, res + (u64)q * rstride);
 	if (launch_aln_wave_batch(c, ap, n, LXmax + 1)) return 1;
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // the one wait
 	for (u32 q = 0; ovf && q < n; ++q) if (ovf[q] & 1u) return 2;
 	for (u32 q = 0; q < n; ++q) {
-		const char *r = res + (u64)q * rstride;
-		u32 n_path;
-		memcpy(&n_path, r, 4);
-		if (n_path > ap[q].LX + ap[q].LY) return fail(c, "mpcgpu_align_pairs: path length %u out of range (internal error)", n_path);
-		pathlens[q] = n_path;
 		float sc;
-		memcpy(&sc, r + 4, 4);
+		if (aln_rec_read(c, "mpcgpu_align_pairs", res + (u64)q * rstride, ap[q].LX, ap[q].LY, paths + (u64)q * path_stride, &pathlens[q], &sc)) return 1;
 		if (scores) scores[q] = sc;
 		if (ea) ea[q] = sc / (float)std::min(ap[q].LX, ap[q].LY); // alignpairflat.cpp:18 (uint -> float, IEEE divide)
-		memcpy(paths + (u64)q * path_stride, r + 8, n_path);
 	}
 	return 0;
 }
@@ -699,7 +671,7 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 	u32 Lsum_max = 0;
 	for (u32 q = 0; q < np; ++q) {
 		const u32 LX = c->len[px[q]], LY = c->len[py[q]];
-		if ((u64)LY + 1 > MPC_ALNW_MAXW || (size_t)(LX + 1) * MPC_ALNW_ROWBYTES + 16 > 160u * 1024u) return 2; // not a one-wave alignment
+		if (!aln_wave_fits(LX, LY)) return 2; // not a one-wave alignment
 		Lsum_max = std::max(Lsum_max, LX + LY);
 	}
 	if (!post_rows_fits(g.LXmax, g.LYmax, 1024)) return 2;
@@ -751,11 +723,86 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 	return 0;
 }
 
+// How many of the first nq pairs of (sx, sy) keep their dense matrices (LX * LY floats each) together in d_aln_post: a chunk whose matrices
+// do not fit half of what is free (long pairs: 1.6 GB for 20 000 x 20 000) is halved like one that stage A has to split, down to a single pair
+static int pairs_that_fit(mpcgpu_ctx *c, const u32 *sx, const u32 *sy, u32 *nq)
+{
+	size_t freeb = 0, totb = 0;
+	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
+	const u64 room = (u64)((freeb + c->d_aln_post.cap) * 0.5);
+	auto bytes_of = [&](u32 k) { u64 b = 0; for (u32 q = 0; q < k; ++q) b += (u64)c->len[sx[q]] * c->len[sy[q]] * 4; return b; };
+	while (*nq > 1 && bytes_of(*nq) > room) *nq = (*nq + 1) / 2;
+	return 0;
+}
+
+// The dense thresholded posteriors of the nq pairs of the stage-A batch just run, pair q at off[q] of d_aln_post, rebuilt from the
+// candidate lists the batch left behind (every cell with Score >= MIN_SPARSE_SCORE, also those FromPost drops)
+static int dense_posts(mpcgpu_ctx *c, u32 nq, const std::vector<u64> &off)
+{
+	// Without the row-list finishing kernel the candidate lists still hold the scores (post_kernel sorts a copy): the raw builder forms
+	// the probabilities itself. Only a list that does not FIT the row-list kernel goes that way; MPCGPU_POST=sort stays a refusal.
+	const char *post_mode = getenv("MPCGPU_POST");
+	if (!c->sa_post_rows && post_mode && !strcmp(post_mode, "sort"))
+		return fail(c, "mpcgpu_align_pairs: pair list with a sequence of more than ~12 000 residues (or MPCGPU_POST=sort): the row-list finishing kernel "
+			"whose candidate lists this entry point rebuilds the dense posteriors from does not take them");
+	HIPCHK(c, c->d_aln_post.ensure_grow(off[nq] * 4));
+	if (upload(c, c->d_ap_off, off)) return 1;
+	DensePostParams dp;
+	dp.pair_x = c->d_bx.as<u32>(); dp.pair_y = c->d_by.as<u32>(); dp.seq_len = c->d_seq_len.as<u32>();
+	dp.cand = c->d_cand.as<u64>(); dp.capc = c->sa_capc; dp.cand_cnt = c->d_cand_cnt.as<u32>(); dp.long_min = c->sa_long_min;
+	dp.out_off = c->d_ap_off.as<u64>(); dp.out = c->d_aln_post.as<float>();
+	if (c->sa_post_rows) MPC_LAUNCH(dense_post_kernel, nq, 256, 0, c->stream, dp);
+	else {
+		// zeroes by one memset on the stream, the scatter on (pairs) x (slabs of 256 candidates, as many as keep the chip busy)
+		DensePostRawParams rp;
+		rp.d = dp; rp.use_fma = c->use_fma;
+		rp.slabs = (u32)std::max<u64>(1, std::min<u64>(((u64)c->sa_capc + 255) / 256, ((u64)c->prop.multiProcessorCount * 8 + nq - 1) / nq));
+		if (trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs dense posteriors from raw candidates: %u pairs x %u slabs, %.1f MB\n", nq, rp.slabs, (double)off[nq] * 4 / 1048576.0); fflush(stderr); }
+		TimedSpan ts_dense;
+		if (span_begin(c, 5, &ts_dense)) return 1;
+		HIPCHK(c, hipMemsetAsync(c->d_aln_post.p, 0, off[nq] * 4, c->stream));
+		MPC_LAUNCH(dense_post_raw_kernel, nq * rp.slabs, 256, 0, c->stream, rp);
+		HIPCHK(c, hipGetLastError());
+		if (span_end(c, &ts_dense)) return 1;
+	}
+	HIPCHK(c, hipGetLastError());
+	c->last_post_cells = 0; // several matrices: not what mpcgpu_get_last_post hands out
+	return 0;
+}
+
+// CalcAlnFlat on the nq dense matrices: one wavefront each in ONE launch when they all fit, else one after the other
+static int align_dense(mpcgpu_ctx *c, u32 nq, const u32 *sx, const u32 *sy, const std::vector<u64> &off, u32 path_stride, char *paths, u32 *pathlens, float *scores, float *ea)
+{
+	u32 Lsum_max = 0, LXmax = 0;
+	bool all_wave = true;
+	for (u32 q = 0; q < nq; ++q) {
+		const u32 LX = c->len[sx[q]], LY = c->len[sy[q]];
+		Lsum_max = std::max(Lsum_max, LX + LY);
+		LXmax = std::max(LXmax, LX);
+		all_wave = all_wave && aln_wave_fits(LX, LY);
+	}
+	if (all_wave) {
+		// one launch: parameters in, {length, score, path} out through page-locked memory
+		HIPCHK(c, c->h_ap.ensure((u64)nq * (sizeof(AlnParams) + aln_rec_stride(Lsum_max))));
+		HIPCHK(c, c->d_aln_rev.ensure_grow((u64)nq * Lsum_max + 16));
+		AlnParams *ap = c->h_ap.as<AlnParams>();
+		return align_wave_batch(c, nq, sx, sy, off.data(), LXmax, Lsum_max, ap, (char *)(ap + nq), nullptr, path_stride, paths, pathlens, scores, ea);
+	}
+	for (u32 q = 0; q < nq; ++q) {
+		const u32 LX = c->len[sx[q]], LY = c->len[sy[q]];
+		float sc = 0;
+		if (run_calc_aln(c, c->d_aln_post.as<float>() + off[q], LX, LY, paths + (u64)q * path_stride, &pathlens[q], &sc)) return 1;
+		if (scores) scores[q] = sc;
+		if (ea) ea[q] = sc / (float)std::min(LX, LY);
+	}
+	return 0;
+}
+
 struct KeepList { mpcgpu_ctx *c; ~KeepList() { c->ap_keep = false; } }; // c->ap_keep (set by the owner) is dropped on every way out
 // AlignPairFlat (alignpairflat.cpp:3-27) for a list of pairs: CalcPost (fwd + bwd + CalcPostFlat, calcpost.cpp:4-36) -> CalcAlnFlat on
 // the DENSE thresholded posterior -> path; EA = Score / min(L1, L2). Stage A runs on the list (the kernels of
-// mpcgpu_calc_posteriors), the dense matrices are rebuilt from the candidate lists (every cell with Score >= MIN_SPARSE_SCORE, also
-// those FromPost drops), the alignments run one wavefront each in ONE launch when they fit (else one after the other).
+// mpcgpu_calc_posteriors), the dense matrices are rebuilt from the candidate lists (dense_posts), the alignments run one wavefront
+// each in ONE launch when they fit (else one after the other: align_dense).
 int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, const uint32_t *seq2, uint32_t path_stride, char *paths,
 	uint32_t *pathlens, float *scores, float *ea)
 {
@@ -782,80 +829,23 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 	c->ap_keep = true;
 	c->ap_x.assign(seq1, seq1 + npairs); c->ap_y.assign(seq2, seq2 + npairs);
 	for (u32 q0 = 0; q0 < npairs;) {
+		const u32 *sx = seq1 + q0, *sy = seq2 + q0;
 		u32 nq = std::min<u32>(chunk, npairs - q0);
-		// the chunk's dense matrices live together in d_aln_post: a chunk whose matrices do not fit half of what is free (long pairs: 1.6 GB
-		// for 20 000 x 20 000) is halved like one that stage A has to split, down to a single pair
-		{
-			size_t freeb = 0, totb = 0;
-			HIPCHK(c, hipMemGetInfo(&freeb, &totb));
-			const u64 room = (u64)((freeb + c->d_aln_post.cap) * 0.5);
-			auto bytes_of = [&](u32 k) { u64 b = 0; for (u32 q = 0; q < k; ++q) b += (u64)c->len[seq1[q0 + q]] * c->len[seq2[q0 + q]] * 4; return b; };
-			while (nq > 1 && bytes_of(nq) > room) { nq = (nq + 1) / 2; chunk = nq; }
-		}
-		// the dense matrices below are rebuilt from the candidate lists ONE stage-A batch leaves behind: a chunk that stage A had to
+		if (pairs_that_fit(c, sx, sy, &nq)) return 1;
+		// the dense matrices are rebuilt from the candidate lists ONE stage-A batch leaves behind: a chunk that stage A had to
 		// cut into several batches (long sequences, little free memory) is halved and run again, down to a single pair
 		for (;;) {
-			if (stage_a(c, nq, seq1 + q0, seq2 + q0)) return 1;
+			if (stage_a(c, nq, sx, sy)) return 1;
 			c->list_q0 = q0; // what the last stage holds is pairs [q0, q0 + nq) of the caller's list
 			if (c->sa_b0 == 0 && c->sa_B == nq) break;
-			if (nq == 1) return fail(c, "mpcgpu_align_pairs: pair %u (%u x %u residues) does not fit one stage-A batch", q0, c->len[seq1[q0]], c->len[seq2[q0]]);
+			if (nq == 1) return fail(c, "mpcgpu_align_pairs: pair %u (%u x %u residues) does not fit one stage-A batch", q0, c->len[sx[0]], c->len[sy[0]]);
 			nq = (nq + 1) / 2;
-			chunk = nq;
 		}
-		// Without the row-list finishing kernel the candidate lists still hold the scores (post_kernel sorts a copy): the raw builder forms
-		// the probabilities itself. Only a list that does not FIT the row-list kernel goes that way; MPCGPU_POST=sort stays a refusal.
-		const char *post_mode = getenv("MPCGPU_POST");
-		if (!c->sa_post_rows && post_mode && !strcmp(post_mode, "sort"))
-			return fail(c, "mpcgpu_align_pairs: pair list with a sequence of more than ~12 000 residues (or MPCGPU_POST=sort): the row-list finishing kernel "
-				"whose candidate lists this entry point rebuilds the dense posteriors from does not take them");
-		// dense matrices
+		chunk = std::min(chunk, nq); // a halved chunk stays halved
 		std::vector<u64> off(nq + 1, 0);
-		u32 Lsum_max = 0, LXmax = 0;
-		bool all_wave = true;
-		for (u32 q = 0; q < nq; ++q) {
-			const u32 LX = c->len[seq1[q0 + q]], LY = c->len[seq2[q0 + q]];
-			off[q + 1] = off[q] + (u64)LX * LY;
-			Lsum_max = std::max(Lsum_max, LX + LY);
-			LXmax = std::max(LXmax, LX);
-			all_wave = all_wave && (u64)LY + 1 <= MPC_ALNW_MAXW && (size_t)(LX + 1) * MPC_ALNW_ROWBYTES + 16 <= 160u * 1024u;
-		}
-		HIPCHK(c, c->d_aln_post.ensure_grow(off[nq] * 4));
-		if (upload(c, c->d_ap_off, off)) return 1;
-		DensePostParams dp;
-		dp.pair_x = c->d_bx.as<u32>(); dp.pair_y = c->d_by.as<u32>(); dp.seq_len = c->d_seq_len.as<u32>();
-		dp.cand = c->d_cand.as<u64>(); dp.capc = c->sa_capc; dp.cand_cnt = c->d_cand_cnt.as<u32>(); dp.long_min = c->sa_long_min;
-		dp.out_off = c->d_ap_off.as<u64>(); dp.out = c->d_aln_post.as<float>();
-		if (c->sa_post_rows) MPC_LAUNCH(dense_post_kernel, nq, 256, 0, c->stream, dp);
-		else {
-			// zeroes by one memset on the stream, the scatter on (pairs) x (slabs of 256 candidates, as many as keep the chip busy)
-			DensePostRawParams rp;
-			rp.d = dp; rp.use_fma = c->use_fma;
-			rp.slabs = (u32)std::max<u64>(1, std::min<u64>(((u64)c->sa_capc + 255) / 256, ((u64)c->prop.multiProcessorCount * 8 + nq - 1) / nq));
-			if (trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs dense posteriors from raw candidates: %u pairs x %u slabs, %.1f MB\n", nq, rp.slabs, (double)off[nq] * 4 / 1048576.0); fflush(stderr); }
-			TimedSpan ts_dense;
-			if (span_begin(c, 5, &ts_dense)) return 1;
-			HIPCHK(c, hipMemsetAsync(c->d_aln_post.p, 0, off[nq] * 4, c->stream));
-			MPC_LAUNCH(dense_post_raw_kernel, nq * rp.slabs, 256, 0, c->stream, rp);
-			HIPCHK(c, hipGetLastError());
-			if (span_end(c, &ts_dense)) return 1;
-		}
-		HIPCHK(c, hipGetLastError());
-		c->last_post_cells = 0; // several matrices: not what mpcgpu_get_last_post hands out
-		if (all_wave) {
-			// one launch: parameters in, {length, score, path} out through page-locked memory
-			HIPCHK(c, c->h_ap.ensure((u64)nq * (sizeof(AlnParams) + aln_rec_stride(Lsum_max))));
-			HIPCHK(c, c->d_aln_rev.ensure_grow((u64)nq * Lsum_max + 16));
-			AlnParams *ap = c->h_ap.as<AlnParams>();
-			if (align_wave_batch(c, nq, seq1 + q0, seq2 + q0, off.data(), LXmax, Lsum_max, ap, (char *)(ap + nq), nullptr, path_stride, paths + (u64)q0 * path_stride, pathlens + q0, scores ? scores + q0 : nullptr, ea ? ea + q0 : nullptr)) return 1;
-		} else {
-			for (u32 q = 0; q < nq; ++q) {
-				const u32 LX = c->len[seq1[q0 + q]], LY = c->len[seq2[q0 + q]];
-				float sc = 0;
-				if (run_calc_aln(c, c->d_aln_post.as<float>() + off[q], LX, LY, paths + (u64)(q0 + q) * path_stride, &pathlens[q0 + q], &sc)) return 1;
-				if (scores) scores[q0 + q] = sc;
-				if (ea) ea[q0 + q] = sc / (float)std::min(LX, LY);
-			}
-		}
+		for (u32 q = 0; q < nq; ++q) off[q + 1] = off[q] + (u64)c->len[sx[q]] * c->len[sy[q]];
+		if (dense_posts(c, nq, off)) return 1;
+		if (align_dense(c, nq, sx, sy, off, path_stride, paths + (u64)q0 * path_stride, pathlens + q0, scores ? scores + q0 : nullptr, ea ? ea + q0 : nullptr)) return 1;
 		q0 += nq;
 	}
 	return 0;

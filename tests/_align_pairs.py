@@ -59,15 +59,15 @@ from muscle_amd.synth import make_family
 PAIRS_SMALL_MAX = 64            # mpcgpu_joins.inc: mpcgpu_align_pairs  npairs <= 64 && MPCGPU_PAIRS_SMALL -> align_pairs_small
 LONG_MIN = 64 * 12 + 1          # mpcgpu_stage_a.inc: stage_a_geom()  MPCGPU_FB_LONG_MIN, clamped to [2, 64 * HMAX + 1]
 HMAX = 16                       # kernels_fb.h:47  MPC_HMAX
-ALNW_MAXW = 512                 # kernels_aln.h:107  MPC_ALNW_MAXW: LY + 1 <= 512 for the one-wave alignment (mpcgpu_joins.inc: align_pairs_small)
-ALNW_ROWBYTES = 256             # kernels_aln.h:108  MPC_ALNW_ROWBYTES: (LX + 1) * 256 + 16 <= 160 KB (mpcgpu_joins.inc: align_pairs_small)
+ALNW_MAXW = 512                 # kernels_aln.h:107  MPC_ALNW_MAXW: LY + 1 <= 512 for the one-wave alignment (mpcgpu_joins.inc: aln_wave_fits)
+ALNW_ROWBYTES = 256             # kernels_aln.h:108  MPC_ALNW_ROWBYTES: (LX + 1) * 256 + 16 <= 160 KB (mpcgpu_joins.inc: aln_wave_fits, MPC_LDS_MAX)
 LDS_BYTES = 160 * 1024
 POST_ROWS_LDS = 150 * 1024      # mpcgpu_stage_a.inc: post_rows_fits()  the row-list finishing kernel's LDS arrays
 POST_SORT_CAP = 1024            # mpcgpu_stage_a.inc: stage_a()  MPCGPU_POST_SORT_CAP default
 CAND_PER_ROW = 12               # mpcgpu_stage_a.inc: stage_a_geom()  MPCGPU_CAND_PER_ROW
 CAND_FLOOR = 1024               # mpcgpu_stage_a.inc: stage_a_geom()
 CHUNK = 256                     # mpcgpu_joins.inc: mpcgpu_align_pairs  pairs per stage-A call of the general path
-QUAD_MAXW = 4096                # mpcgpu_joins.inc:13-14  (W + 255) / 256 * 64 <= 1024 threads
+QUAD_MAXW = 4096                # mpcgpu_joins.inc: run_calc_aln  (W + 255) / 256 * 64 <= 1024 threads
 LONG_H = 7                      # mpcgpu.cpp:381  MPC_LONG_H (MPCGPU_FB_LONG_H = 4: MPC_LONG_H_SMALL, 1: one row per lane)
 WAVE, QUAD, LDSROWS = "one wave", "waves, rows in registers", "rows in LDS"
 SHORT_FB = "[mpcgpu] align_pairs short list: fb H="
@@ -101,7 +101,7 @@ def one_wave(LX, LY):
 
 
 def aln_class(LX, LY):
-    """run_calc_aln's choice by size (mpcgpu_joins.inc:9-16)"""
+    """run_calc_aln's choice by size (mpcgpu_joins.inc: aln_wave_fits, run_calc_aln)"""
     if one_wave(LX, LY):
         return WAVE
     if (LY + 1 + 255) // 256 * 64 <= 1024:

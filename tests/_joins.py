@@ -32,7 +32,8 @@ import _oracle as O
 from muscle_amd._lib import MpcGpu
 from muscle_amd.synth import make_family
 
-# the dispatcher's limits (mpcgpu_joins.inc: build_post_impl, mpcgpu_align_alns_batch, run_calc_aln; kernels_prog.h: MPC_BPR_CAP;
+# the dispatcher's limits (mpcgpu_joins.inc: rows_form_fits with MPC_ROWS_PAIRS_MAX, MPC_ROWS_CELLS1_MAX (build_post_impl) and
+# MPC_ROWS_CELLS1_MAX_BATCH (mpcgpu_align_alns_batch), aln_wave_fits with MPC_LDS_MAX, the 1 GiB of cut_join_chunk; kernels_prog.h: MPC_BPR_CAP;
 # kernels_aln.h: MPC_ALNW_MAXW, MPC_ALNW_ROWBYTES)
 ROW_PAIRS, ROW_C2, ROW_CELLS1, BATCH_CELLS1 = 2048, 1024, 1 << 26, 1 << 22
 BPR_CAP, ALNW_MAXW, ALNW_ROWBYTES, LDS_BYTES = 1024, 512, 256, 160 * 1024
