@@ -5,6 +5,9 @@
 # of the reference is copied into the repo, and the combined (GPL-3.0) binary is git-ignored. A copy
 # is kept beside the compiled reference as oracle/_ref/muscle_gpu, which travels with it to a GPU
 # box: where the reference sources are absent, this script installs that copy instead of linking.
+# The copy is also kept under a name that carries a digest of the drop-in's sources (oracle/_ref/muscle_gpu.<digest>): an
+# oracle/_ref that serves several checkouts (two commits built one after the other) holds a binary for each, and a checkout
+# without the reference sources installs the one linked from ITS hostcxx/ — the plain name only when there is none, with a warning.
 #
 #   reference objects  - consflat.o, alnalnsflat.o, alnmsasflat.o, buildpostflat.o, alignpairflat.o, refineflat.o  (MPCFlat::ConsIter,
 #                        MPCFlat::AlignAlns, PProg::AlignMSAsFlat, MPCFlat::BuildPost, AlignPairFlat(_SparsePost) and
@@ -22,11 +25,19 @@ SRC="${MUSCLE_REF_SRC:-/root/reference/src}"
 REFOBJ="$ROOT/oracle/_ref/obj"
 OUT="$HERE/_build"
 PREBUILT="$ROOT/oracle/_ref/muscle_gpu"
+DIGEST=$(cat "$HERE/mpcflat_gpu.cpp" "$HERE/rand_isolate.cpp" "$HERE/build_muscle_gpu.sh" "$ROOT/include/mpcgpu.h" | sha256sum | cut -c1-16)
 if [ ! -d "$SRC" ] || [ ! -d "$REFOBJ" ]; then
+  if [ -z "${MPCGPU_BIN:-}" ] && [ -x "$PREBUILT.$DIGEST" ]; then
+    mkdir -p "$OUT"
+    cp -p "$PREBUILT.$DIGEST" "$OUT/muscle_gpu"
+    echo "installed: $OUT/muscle_gpu (from $PREBUILT.$DIGEST; the reference sources are not here)"
+    exit 0
+  fi
   if [ -z "${MPCGPU_BIN:-}" ] && [ -x "$PREBUILT" ]; then
     mkdir -p "$OUT"
     cp -p "$PREBUILT" "$OUT/muscle_gpu"
     echo "installed: $OUT/muscle_gpu (from $PREBUILT; the reference sources are not here)"
+    echo "build_muscle_gpu.sh: WARNING: no $PREBUILT.$DIGEST - the installed binary may have been linked from other drop-in sources than this tree's hostcxx/" >&2
     exit 0
   fi
   echo "build_muscle_gpu.sh: reference sources/objects not available (run oracle/build_ref.sh where the reference sources are) - skipping" >&2
@@ -66,4 +77,5 @@ echo "built: $OUT/$BIN"
 # the product binary, beside the compiled reference (same depth below the root: the $ORIGIN run path holds from there too)
 if [ -z "${MPCGPU_BIN:-}" ]; then
   cp -p "$OUT/$BIN" "$PREBUILT"
+  cp -p "$OUT/$BIN" "$PREBUILT.$DIGEST"
 fi

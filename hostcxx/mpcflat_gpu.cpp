@@ -59,6 +59,54 @@ extern "C" void MuscleGpuRandThreadEnd(void);
 
 namespace
 {
+// The Mega statics a .mega input fills (mega.h:9-33), flat as mpcgpu_set_mega takes them, with the profiles of one set of sequences:
+// what SetMega uploads, and what a later run is compared with (ensemble reuse, MPCFlat::CalcPosterior).
+struct MegaFlat
+	{
+	bool m_Loaded = false;
+	vector<uint32_t> m_AlphaSizes;		// per feature
+	vector<float> m_Weights;		// per feature
+	vector<vector<float> > m_LogProbs;	// per feature: alpha floats
+	vector<vector<float> > m_Mxs;		// per feature: alpha x alpha floats, row-major
+	vector<vector<uint8_t> > m_Profs;	// per sequence: length x features letters, position-major
+	bool operator==(const MegaFlat &r) const
+		{
+		if (m_Loaded != r.m_Loaded || m_AlphaSizes != r.m_AlphaSizes || m_Profs != r.m_Profs || SIZE(m_Weights) != SIZE(r.m_Weights) ||
+		  SIZE(m_LogProbs) != SIZE(r.m_LogProbs) || SIZE(m_Mxs) != SIZE(r.m_Mxs))
+			return false;
+// floats by their bytes: what the device was given, not what compares equal
+		auto SameBytes = [](const vector<float> &a, const vector<float> &b)
+			{ return SIZE(a) == SIZE(b) && (a.empty() || memcmp(a.data(), b.data(), 4*a.size()) == 0); };
+		if (!SameBytes(m_Weights, r.m_Weights))
+			return false;
+		for (uint f = 0; f < SIZE(m_LogProbs); ++f)
+			if (!SameBytes(m_LogProbs[f], r.m_LogProbs[f]) || !SameBytes(m_Mxs[f], r.m_Mxs[f]))
+				return false;
+		return true;
+		}
+	};
+
+// What the slot's last COMPLETED posterior stage was computed from, byte for byte: the replicates of an ensemble (align.cpp:150-167:
+// -stratified runs MPCFlat::Run four times per perturbation seed on the same MPCFlat and the same input, and the tree permutation
+// enters after the stage, mpcflat.cpp:195) find the store they would compute already on the device. Valid only once the stage and its
+// relax iterations are through: a stage that dies half-way leaves nothing reusable.
+struct KeptStage
+	{
+	bool m_Valid = false;
+	vector<vector<byte> > m_Seqs;		// every byte of every sequence
+	float m_Start[5];
+	float m_Trans[25];
+	vector<float> m_Match;			// 256 x 256
+	float m_Ins[256];
+	float m_MinSparseScore = 0;
+	MegaFlat m_Mega;
+	uint m_ConsistencyIterCount = 0;
+	vector<int> m_Devices;			// DeviceList() of the run
+	const void *m_Ctx = 0;			// the slot's context and group
+	const void *m_Group = 0;
+	vector<uint64_t> m_Epochs;		// mpcgpu_store_epoch of the slot's context (of every context of its group) when the stage was complete
+	};
+
 struct Batch
 	{
 	const MultiSequence *m_Seqs = 0;
@@ -67,6 +115,8 @@ struct Batch
 	bool m_Materialise = false; // host copies of the stage-A matrices are needed (no relax follows)
 	bool m_OnHost = false;	// the CURRENT device matrices have been copied into the MySparseMx objects
 	uint m_ItersDone = 0;	// ConsIter calls since the batch started
+	uint m_StoreIters = 0;	// relax iterations the device store holds: ConsIter(Iter) below that number has nothing to compute (a reused stage)
+	KeptStage m_Kept;
 	unsigned long long m_Gen = 0;	// which StartBatch this is (process-wide count): what state derived from the batch is checked against
 	vector<float> m_EA;	// what calcposteriorflat.cpp:89 stores in m_DistMx
 // what the batch was computed from: a caller that re-runs InitSeqs on the same MPCFlat object (cmd_profseq does, with a
@@ -114,6 +164,31 @@ Slot g_Slots[MAX_SLOTS];
 std::mutex g_MapMu;	// guards the two maps (not the batches themselves: a batch is used under its slot's mutex)
 std::map<const MPCFlat *, Batch> g_Batches;
 std::map<const MPCFlat *, int> g_SlotOf;
+// MPCFlat::RefineIter's alignment as position -> column maps (see there), per MPCFlat object
+struct RefineState
+	{
+	const MultiSequence *m_MSA = 0;
+	unsigned long long m_BatchGen = 0;
+	uint m_ColCount = 0;
+	vector<uint32_t> m_Seq;			// row -> index in m_MyInputSeqs
+	vector<vector<uint32_t> > m_Map;	// row -> position -> column
+	vector<string> m_Letters;		// row -> its residues (the non-gap characters of the row)
+	};
+std::map<const MPCFlat *, RefineState> g_Refine;	// (guarded by g_MapMu)
+std::atomic<unsigned long long> g_BatchGen(0);	// batches started or reused in this process
+// MUSCLE_GPU_TIMING: MPCFlat::Runs that reached CalcPosteriors, by whether their stage ran or was found on the device
+std::atomic<unsigned long long> g_StagesComputed(0), g_StagesReused(0);
+
+// A batch takes a new generation: what was derived from the previous one (RefineIter's maps) is dropped. The entry is reset in
+// place (RefineIter holds a pointer to it), under the lock of the maps.
+void NewGeneration(const MPCFlat *M, Batch &B)
+	{
+	B.m_Gen = ++g_BatchGen;
+	std::lock_guard<std::mutex> Guard(g_MapMu);
+	std::map<const MPCFlat *, RefineState>::iterator p = g_Refine.find(M);
+	if (p != g_Refine.end())
+		p->second = RefineState();
+	}
 // PProg joins and pair lists (AlignMSAsFlat, AlignPairFlat, UClust::Search): contexts of their own, so that they never disturb the
 // store of an MPCFlat run — ONE PER LISTED DEVICE (MUSCLE_GPU_DEVICES), each under its own mutex. A calling thread keeps the join
 // context it was dealt: the worker threads of the parallel shrub loop that of their slot's device (so a shrub's joins run where
@@ -339,6 +414,7 @@ bool TimingOn()
 				fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  (inside the first call below that needed it)\n", "context creation, HIP init", g_CtxSeconds);
 				for (int i = 0; i < T_COUNT; ++i)
 					fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  %8llu calls\n", Names[i], g_Nanos[i].load()*1e-9, g_Calls[i].load());
+				fprintf(stderr, "[muscle_gpu] posterior stage: computed %llu reused %llu\n", g_StagesComputed.load(), g_StagesReused.load());
 // (one MPCFlat::Run only: with the shrub workers of -super7 running many at once first-entered / last-left marks interleave)
 				const bool OneRun = g_Mark[M_POST_ENTER].load() != 0 && g_Mark[M_POST_ENTER].load() <= g_Mark[M_POST_EXIT].load() &&
 				  (g_Mark[M_CONS_ENTER].load() == 0 || (g_Mark[M_POST_EXIT].load() <= g_Mark[M_CONS_ENTER].load() && g_Mark[M_CONS_EXIT].load() <= std::max(g_Mark[M_ALN_ENTER].load(), g_Mark[M_CONS_EXIT].load()))) &&
@@ -481,59 +557,158 @@ template<class GETMX> void Download(mpcgpu_ctx *Ctx, MPCFlat &M, uint PairCount,
 // calcpost.cpp:14-22: with a .mega input loaded the emissions come from the structure profiles of the
 // sequences (looked up by label, like CalcPost does), not from the PairHMM letter tables. Labels[i] is
 // the label of sequence i of the set just given to mpcgpu_set_seqs / mpcgpu_set_seqs_registry.
-void SetMega(mpcgpu_ctx *Ctx, const vector<string> &Labels, const vector<uint32_t> &Lens, mpcgpu_group *Group = 0)
+void FlattenMega(const vector<string> &Labels, const vector<uint32_t> &Lens, MegaFlat &F)
 	{
+	F = MegaFlat();
+	F.m_Loaded = Mega::m_Loaded;
 	if (!Mega::m_Loaded)
-		return; // set_seqs already switched the context back to letter emissions
+		return;
 	const uint FeatureCount = Mega::GetFeatureCount();
-	vector<uint32_t> AlphaSizes(FeatureCount);
-	vector<float> Weights(FeatureCount);
-	vector<vector<float> > Mxs(FeatureCount);
-	vector<const float *> LogProbPtrs(FeatureCount), MxPtrs(FeatureCount);
+	F.m_AlphaSizes.resize(FeatureCount);
+	F.m_Weights.resize(FeatureCount);
+	F.m_LogProbs.resize(FeatureCount);
+	F.m_Mxs.resize(FeatureCount);
 	for (uint f = 0; f < FeatureCount; ++f)
 		{
 		const uint A = Mega::GetAlphaSize(f);
-		AlphaSizes[f] = A;
-		Weights[f] = Mega::GetWeight(f);
+		F.m_AlphaSizes[f] = A;
+		F.m_Weights[f] = Mega::GetWeight(f);
 		asserta(SIZE(Mega::m_LogProbsVec[f]) == A);
-		LogProbPtrs[f] = Mega::m_LogProbsVec[f].data();
+		F.m_LogProbs[f] = Mega::m_LogProbsVec[f];
 		const vector<vector<float> > &Mx = Mega::m_LogProbMxVec[f];
 		asserta(SIZE(Mx) == A);
 		for (uint a = 0; a < A; ++a)
 			{
 			asserta(SIZE(Mx[a]) == A);
-			Mxs[f].insert(Mxs[f].end(), Mx[a].begin(), Mx[a].end());
+			F.m_Mxs[f].insert(F.m_Mxs[f].end(), Mx[a].begin(), Mx[a].end());
 			}
-		MxPtrs[f] = Mxs[f].data();
 		}
 	const uint SeqCount = SIZE(Labels);
-	vector<vector<uint8_t> > Profs(SeqCount);
-	vector<const uint8_t *> ProfPtrs(SeqCount);
+	F.m_Profs.resize(SeqCount);
 	for (uint i = 0; i < SeqCount; ++i)
 		{
 		const vector<vector<byte> > &Profile = *Mega::GetProfileByLabel(Labels[i]);
 		asserta(SIZE(Profile) == Lens[i]); // calcpost.cpp:18-19
-		Profs[i].reserve(size_t(Lens[i])*FeatureCount);
+		F.m_Profs[i].reserve(size_t(Lens[i])*FeatureCount);
 		for (uint Pos = 0; Pos < Lens[i]; ++Pos)
 			{
 			asserta(SIZE(Profile[Pos]) == FeatureCount);
-			Profs[i].insert(Profs[i].end(), Profile[Pos].begin(), Profile[Pos].end());
+			F.m_Profs[i].insert(F.m_Profs[i].end(), Profile[Pos].begin(), Profile[Pos].end());
 			}
-		ProfPtrs[i] = Profs[i].data();
 		}
+	}
+
+void SetMega(mpcgpu_ctx *Ctx, const MegaFlat &F, mpcgpu_group *Group = 0)
+	{
+	if (!F.m_Loaded)
+		return; // set_seqs already switched the context back to letter emissions
+	const uint FeatureCount = SIZE(F.m_AlphaSizes);
+	vector<const float *> LogProbPtrs(FeatureCount), MxPtrs(FeatureCount);
+	for (uint f = 0; f < FeatureCount; ++f)
+		{
+		LogProbPtrs[f] = F.m_LogProbs[f].data();
+		MxPtrs[f] = F.m_Mxs[f].data();
+		}
+	vector<const uint8_t *> ProfPtrs(SIZE(F.m_Profs));
+	for (uint i = 0; i < SIZE(F.m_Profs); ++i)
+		ProfPtrs[i] = F.m_Profs[i].data();
 	if (Group != 0)
-		GRPCHK(mpcgpu_group_set_mega(Group, FeatureCount, AlphaSizes.data(), Weights.data(), LogProbPtrs.data(),
+		GRPCHK(mpcgpu_group_set_mega(Group, FeatureCount, F.m_AlphaSizes.data(), F.m_Weights.data(), LogProbPtrs.data(),
 		  MxPtrs.data(), ProfPtrs.data()));
 	else
-		GPUCHK(mpcgpu_set_mega(Ctx, FeatureCount, AlphaSizes.data(), Weights.data(), LogProbPtrs.data(),
+		GPUCHK(mpcgpu_set_mega(Ctx, FeatureCount, F.m_AlphaSizes.data(), F.m_Weights.data(), LogProbPtrs.data(),
 		  MxPtrs.data(), ProfPtrs.data()));
+	}
+
+void SetMega(mpcgpu_ctx *Ctx, const vector<string> &Labels, const vector<uint32_t> &Lens, mpcgpu_group *Group = 0)
+	{
+	MegaFlat F;
+	FlattenMega(Labels, Lens, F);
+	SetMega(Ctx, F, Group);
+	}
+
+// mpcgpu_store_epoch of the slot's context, or of every context of its group
+vector<uint64_t> EpochsOf(const Slot &S)
+	{
+	const uint32_t n = S.m_Group != 0 ? mpcgpu_group_size(S.m_Group) : 1;
+	vector<uint64_t> Epochs(n);
+	for (uint32_t r = 0; r < n; ++r)
+		{
+		mpcgpu_ctx *Rank = S.m_Group != 0 ? mpcgpu_group_ctx(S.m_Group, r) : S.m_Ctx;
+		if (mpcgpu_store_epoch(Rank, &Epochs[r]) != 0)
+			Die("GPU posterior stage: %s", mpcgpu_last_error(Rank));
+		}
+	return Epochs;
+	}
+
+bool ReuseEnv()
+	{
+	static int On = -1;
+	if (On < 0)
+		{
+		const char *s = getenv("MUSCLE_GPU_ENSEMBLE_REUSE");
+		On = (s != 0 && *s == '0') ? 0 : 1;
+		}
+	return On == 1;
+	}
+
+// Is the stage this Run would compute the one the slot's store holds? What the Run would upload is compared with what the kept
+// stage was computed from, every byte of it, and the contexts' epochs say that nothing has touched them since. Returns 0 when the
+// store can be reused, else what differs. Call with the slot's mutex held.
+const char *WhyNotReusable(MPCFlat &M, const Batch &B, const Slot &S)
+	{
+	const KeptStage &K = B.m_Kept;
+	if (!ReuseEnv())
+		return "switched off";
+	if (!K.m_Valid)
+		return "no completed stage kept";
+	const uint SeqCount = M.GetSeqCount();
+	if (SIZE(K.m_Seqs) != SeqCount || B.m_PairCount != SIZE(M.m_Pairs) || SIZE(B.m_EA) != B.m_PairCount)
+		return "sequence count";
+	for (uint i = 0; i < SeqCount; ++i)
+		{
+		const uint L = M.GetSeqLength(i);
+		if (SIZE(K.m_Seqs[i]) != L || (L != 0 && memcmp(K.m_Seqs[i].data(), M.GetBytePtr(i), L) != 0))
+			return "sequences";
+		}
+	const float MinSparseScore = MIN_SPARSE_SCORE;
+	if (memcmp(K.m_Start, PairHMM::m_StartScore, sizeof(K.m_Start)) != 0 || memcmp(K.m_Trans, PairHMM::m_TransScore, sizeof(K.m_Trans)) != 0 ||
+	  memcmp(K.m_Match.data(), PairHMM::m_MatchScore, sizeof(PairHMM::m_MatchScore)) != 0 ||
+	  memcmp(K.m_Ins, PairHMM::m_InsScore, sizeof(K.m_Ins)) != 0 || memcmp(&K.m_MinSparseScore, &MinSparseScore, sizeof(float)) != 0)
+		return "PairHMM tables";
+	if (K.m_Mega.m_Loaded != Mega::m_Loaded)
+		return "Mega state";
+	if (Mega::m_Loaded)
+		{
+		vector<string> Labels(SeqCount);
+		vector<uint32_t> Lens(SeqCount);
+		for (uint i = 0; i < SeqCount; ++i)
+			{
+			Labels[i] = string(M.GetLabel(i));
+			Lens[i] = M.GetSeqLength(i);
+			}
+		MegaFlat Now;
+		FlattenMega(Labels, Lens, Now);
+		if (!(K.m_Mega == Now))
+			return "Mega state";
+		}
+	if (K.m_ConsistencyIterCount != M.m_ConsistencyIterCount)
+		return "consistency iterations";
+	if (!B.m_Materialise && B.m_StoreIters != K.m_ConsistencyIterCount)
+		return "relax iterations in the store";
+	if (K.m_Devices != DeviceList() || K.m_Ctx != (const void *) S.m_Ctx || K.m_Group != (const void *) S.m_Group || S.m_Ctx == 0)
+		return "devices";
+	if (S.m_StoreOwner != &M)
+		return "store owner";
+	if (K.m_Epochs != EpochsOf(S))
+		return "store epoch";
+	return 0;
 	}
 
 // First CalcPosterior call of a run: the whole all-pairs stage A on the device.
 void StartBatch(MPCFlat &M, Batch &B, int SlotIndex)
 	{
-	static std::atomic<unsigned long long> s_Gen(0);
-	B.m_Gen = ++s_Gen;
+	NewGeneration(&M, B);
 	Stopwatch SW(T_STAGE_A);
 	mpcgpu_ctx *Ctx = GetCtx(SlotIndex);
 	mpcgpu_group *Group = g_Slots[SlotIndex].m_Group;
@@ -559,17 +734,19 @@ void StartBatch(MPCFlat &M, Batch &B, int SlotIndex)
 		Labels[i] = string(M.GetLabel(i)); // calcposteriorflat.cpp:63-64
 		}
 // (the "HMM overflow" length check of calcposteriorflat.cpp:54-61 is made by the library)
+	MegaFlat MegaNow;
+	FlattenMega(Labels, Lens, MegaNow);
 	if (Group != 0)
 		{
 // mpcflat.cpp:239-251 sharded over the devices + the all-gather of the sparse posteriors (mpcgpu_group.cpp)
 		GRPCHK(mpcgpu_group_set_seqs(Group, SeqCount, Ptrs.data(), Lens.data()));
-		SetMega(Ctx, Labels, Lens, Group);
+		SetMega(Ctx, MegaNow, Group);
 		GRPCHK(mpcgpu_group_calc_posteriors(Group));
 		}
 	else
 		{
 		GPUCHK(mpcgpu_set_seqs(Ctx, SeqCount, Ptrs.data(), Lens.data()));
-		SetMega(Ctx, Labels, Lens);
+		SetMega(Ctx, MegaNow);
 		GPUCHK(mpcgpu_calc_posteriors(Ctx, 0, PairCount));
 		GPUCHK(mpcgpu_build_store(Ctx));
 		}
@@ -579,6 +756,7 @@ void StartBatch(MPCFlat &M, Batch &B, int SlotIndex)
 	B.m_Served = 0;
 	B.m_OnHost = false;
 	B.m_ItersDone = 0;
+	B.m_StoreIters = 0;
 	B.m_SeqPtrs.assign(Ptrs.begin(), Ptrs.end());
 	B.m_SeqLens.assign(Lens.begin(), Lens.end());
 	B.m_SeqEnds.resize(SeqCount);
@@ -597,6 +775,27 @@ void StartBatch(MPCFlat &M, Batch &B, int SlotIndex)
 // MPCFlat::Consistency (mpcflat.cpp:173-181) is skipped for < 3 sequences or 0 iterations: then the
 // progressive stage reads the stage-A matrices, so they must exist on the host.
 	B.m_Materialise = (SeqCount < 3 || M.m_ConsistencyIterCount == 0);
+// what this stage was computed from, for the next Run on this MPCFlat (WhyNotReusable). With relax iterations to come it is complete
+// after the last of them (MPCFlat::ConsIter), without any it is complete here.
+		{
+		KeptStage &K = B.m_Kept;
+		K.m_Seqs.resize(SeqCount);
+		for (uint i = 0; i < SeqCount; ++i)
+			K.m_Seqs[i].assign(Ptrs[i], Ptrs[i] + Lens[i]);
+		memcpy(K.m_Start, PairHMM::m_StartScore, sizeof(K.m_Start));
+		memcpy(K.m_Trans, PairHMM::m_TransScore, sizeof(K.m_Trans));
+		K.m_Match.assign(&PairHMM::m_MatchScore[0][0], &PairHMM::m_MatchScore[0][0] + 256*256);
+		memcpy(K.m_Ins, PairHMM::m_InsScore, sizeof(K.m_Ins));
+		K.m_MinSparseScore = MIN_SPARSE_SCORE;
+		K.m_Mega = std::move(MegaNow);
+		K.m_ConsistencyIterCount = M.m_ConsistencyIterCount;
+		K.m_Devices = DeviceList();
+		K.m_Ctx = Ctx;
+		K.m_Group = Group;
+		K.m_Epochs = EpochsOf(g_Slots[SlotIndex]);
+		K.m_Valid = B.m_Materialise;
+		}
+	++g_StagesComputed;
 	if (DebugOn())
 		{
 		uint64_t h = Fnv(14695981039346656037ull, B.m_EA.data(), 4*size_t(PairCount));
@@ -610,6 +809,25 @@ void StartBatch(MPCFlat &M, Batch &B, int SlotIndex)
 		fprintf(stderr, "[muscle_gpu] stage A: %u seqs fnv(seqs) %016llx fnv(hmm) %016llx fnv(EA) %016llx\n", SeqCount,
 		  (unsigned long long) hs, (unsigned long long) hh, (unsigned long long) h);
 		}
+	}
+
+// The Run's stage is the one on the device (WhyNotReusable said so): no uploads, no stage A, no store build. The batch points at this
+// Run's sequence objects, serves the kept EAs and takes a new generation; the store's relax iterations stay counted, so that
+// MPCFlat::ConsIter finds them done.
+void ReuseBatch(MPCFlat &M, Batch &B)
+	{
+	NewGeneration(&M, B);
+	const uint SeqCount = M.GetSeqCount();
+	B.m_Seqs = M.m_MyInputSeqs;
+	B.m_Served = 0;
+	B.m_OnHost = false; // (MPCFlat::Clear freed the host matrices)
+	B.m_ItersDone = 0;
+	B.m_SeqPtrs.resize(SeqCount);
+	for (uint i = 0; i < SeqCount; ++i)
+		B.m_SeqPtrs[i] = M.GetBytePtr(i); // (lengths and content hashes are the kept stage's: compared byte for byte)
+	++g_StagesReused;
+	if (DebugOn())
+		fprintf(stderr, "[muscle_gpu] stage A reused: %u seqs, store holds %u relax iterations, generation %llu\n", SeqCount, B.m_StoreIters, B.m_Gen);
 	}
 } // namespace
 
@@ -662,7 +880,18 @@ void MPCFlat::CalcPosterior(uint PairIndex)
 			}
 		if (!Fresh)
 			{
-			StartBatch(*this, B, SlotIndex);
+// an ensemble's next replicate (align.cpp:150-167) on the same input with the same tables: the stage and its relax iterations are
+// already in the device store, bit for bit. Anything else: the kept state is forgotten BEFORE the new stage starts.
+			const char *Why = WhyNotReusable(*this, B, S);
+			if (Why == 0)
+				ReuseBatch(*this, B);
+			else
+				{
+				if (DebugOn() && B.m_Kept.m_Valid)
+					fprintf(stderr, "[muscle_gpu] stage A not reused: %s\n", Why);
+				B.m_Kept = KeptStage();
+				StartBatch(*this, B, SlotIndex);
+				}
 			if (B.m_Materialise && DownloadOn())
 				{
 				Download(S.m_Ctx, *this, B.m_PairCount, [this](uint k) -> MySparseMx & { return GetSparsePost(k); });
@@ -696,12 +925,24 @@ void MPCFlat::ConsIter(uint Iter)
 		Batch &B = BatchOf(this);
 		++B.m_ItersDone;
 		B.m_OnHost = false;
-		if (Group != 0)
-			GRPCHK(mpcgpu_group_cons_iter(Group)); // consflat.cpp:5-23 sharded + the all-gather of the new values
-		else
+// (a reused stage, MPCFlat::CalcPosterior: the store already holds this iteration — nothing to compute, the rest as ever)
+		if (Iter >= B.m_StoreIters)
 			{
-			GPUCHK(mpcgpu_cons_iter(Ctx, 0, PairCount));
-			GPUCHK(mpcgpu_cons_commit(Ctx));
+			B.m_Kept.m_Valid = false;
+			if (Group != 0)
+				GRPCHK(mpcgpu_group_cons_iter(Group)); // consflat.cpp:5-23 sharded + the all-gather of the new values
+			else
+				{
+				GPUCHK(mpcgpu_cons_iter(Ctx, 0, PairCount));
+				GPUCHK(mpcgpu_cons_commit(Ctx));
+				}
+			++B.m_StoreIters;
+			if (B.m_StoreIters == m_ConsistencyIterCount && m_ConsistencyIterCount == B.m_Kept.m_ConsistencyIterCount && !B.m_Kept.m_Seqs.empty())
+				{
+// the stage is complete: what it was computed from (StartBatch) may serve the next Run while the epochs stay where they are now
+				B.m_Kept.m_Epochs = EpochsOf(S);
+				B.m_Kept.m_Valid = true;
+				}
 			}
 // Nothing on the host reads the matrices any more (ProgressiveAlign/Refine -> AlignAlns below);
 // they are downloaded after the last iteration only on request.
@@ -794,8 +1035,6 @@ MultiSequence *MPCFlat::AlignAlns(const MultiSequence &MSA1,
 
 	const int SlotIndex = SlotIndexOf(this);
 	Slot &S = g_Slots[SlotIndex];
-	if (S.m_StoreOwner != this)
-		Die("GPU posterior stage: AlignAlns on an MPCFlat whose posteriors are not the ones on the device");
 	Stopwatch SW(T_ALN_PREP);
 	vector<uint32_t> Seqs1(SeqCount1), Seqs2(SeqCount2);
 	vector<uint32_t> Map1, Map2;
@@ -827,6 +1066,8 @@ MultiSequence *MPCFlat::AlignAlns(const MultiSequence &MSA1,
 	SW.Next(T_ALN_LIB);
 		{
 		std::lock_guard<std::mutex> Guard(S.m_Mu);
+		if (S.m_StoreOwner != this) // (checked under the slot's lock, as in BuildPost)
+			Die("GPU posterior stage: AlignAlns on an MPCFlat whose posteriors are not the ones on the device");
 		mpcgpu_ctx *Ctx = GetCtx(SlotIndex);
 		GPUCHK(mpcgpu_align_alns_w(Ctx, SeqCount1, Seqs1.data(), SeqCount2, Seqs2.data(), ColCount1, ColCount2,
 		  Map1.data(), Map2.data(), W1.data(), W2.data(), &Path[0], &PathLen, &Score));
@@ -884,7 +1125,12 @@ void MPCFlat::ProgressiveAlign()
 		}
 	const int SlotIndex = SlotIndexOf(this);
 	Slot &S = g_Slots[SlotIndex];
-	if (!Plain || S.m_StoreOwner != this || JoinCount < 2)
+	bool Owner;
+		{
+		std::lock_guard<std::mutex> Guard(S.m_Mu);
+		Owner = (S.m_StoreOwner == this);
+		}
+	if (!Plain || !Owner || JoinCount < 2)
 		{
 // the reference's own function (progalnflat.cpp:72-100), kept in the binary under another name (hostcxx/build_muscle_gpu.sh: objcopy
 // --redefine-sym on progalnflat.o): its joins go through MPCFlat::AlignAlns above, one after the other
@@ -1016,20 +1262,6 @@ void MPCFlat::ProgressiveAlign()
 // O(residues) per round; m_MSA is rebuilt from the maps after every round (a character matrix filled once), so it is valid whenever
 // anybody looks. The rand() calls are the reference's, one per row, in row order; the numeric part is mpcgpu_align_alns_w as in
 // MPCFlat::AlignAlns above. State is kept per MPCFlat object and checked against m_MSA's address and the posterior batch it belongs to.
-namespace
-{
-struct RefineState
-	{
-	const MultiSequence *m_MSA = 0;
-	unsigned long long m_BatchGen = 0;
-	uint m_ColCount = 0;
-	vector<uint32_t> m_Seq;			// row -> index in m_MyInputSeqs
-	vector<vector<uint32_t> > m_Map;	// row -> position -> column
-	vector<string> m_Letters;		// row -> its residues (the non-gap characters of the row)
-	};
-std::map<const MPCFlat *, RefineState> g_Refine;	// (guarded by g_MapMu)
-}
-
 void MPCFlat::RefineIter()
 	{
 	const uint SeqCount = GetSeqCount();
@@ -1083,8 +1315,11 @@ void MPCFlat::RefineIter()
 	if (Rows1.empty() || Rows2.empty())
 		return;
 
-	if (S.m_StoreOwner != this)
-		Die("GPU posterior stage: RefineIter on an MPCFlat whose posteriors are not the ones on the device");
+		{
+		std::lock_guard<std::mutex> Guard(S.m_Mu);
+		if (S.m_StoreOwner != this)
+			Die("GPU posterior stage: RefineIter on an MPCFlat whose posteriors are not the ones on the device");
+		}
 	PhaseMark(M_ALN_ENTER, true);
 	struct ExitMark { ~ExitMark() { PhaseMark(M_ALN_EXIT, false); } } MarkAtExit;
 	Stopwatch SW(T_ALN_PREP);
@@ -1126,6 +1361,8 @@ void MPCFlat::RefineIter()
 	SW.Next(T_ALN_LIB);
 		{
 		std::lock_guard<std::mutex> Guard(S.m_Mu);
+		if (S.m_StoreOwner != this) // (again under the lock the call runs under: another MPCFlat's batch may have taken the context over)
+			Die("GPU posterior stage: RefineIter on an MPCFlat whose posteriors are not the ones on the device");
 		mpcgpu_ctx *Ctx = GetCtx(SlotIndex);
 		GPUCHK(mpcgpu_align_alns_w(Ctx, SIZE(Seqs1), Seqs1.data(), SIZE(Seqs2), Seqs2.data(), ColCount1, ColCount2,
 		  Map1.data(), Map2.data(), W1.data(), W2.data(), &Path[0], &PathLen, &Score));
@@ -1714,6 +1951,7 @@ void Super7::IntraAlignShrubs()
 				std::lock_guard<std::mutex> Guard(g_MapMu);
 				g_SlotOf.erase(&Local);
 				g_Batches.erase(&Local);
+				g_Refine.erase(&Local);
 				}
 			g_Slots[1 + w].m_StoreOwner = 0; // Local dies with this thread
 			});

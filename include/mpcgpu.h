@@ -90,6 +90,31 @@ int mpcgpu_set_mega(mpcgpu_ctx *ctx, uint32_t nfeat, const uint32_t *alpha, cons
 
 uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
 
+/* ---- the store epoch -----------------------------------------------------------------------------------------
+ * A counter that moves whenever anything a reader of this context's store could observe may have changed: a caller that has
+ * fingerprinted what a store was computed from (the drop-in: the replicates of an ensemble, align.cpp:150-167, run MPCFlat::Run
+ * on the same input with the same tables) keeps the epoch beside the fingerprint, and an equal epoch later says the store, the
+ * tables, the sequences and the committed values are still the memory it left. One uint64_t in the context, no device work.
+ * 0 after mpcgpu_create. Every entry of this header is on one side:
+ *   MOVES IT (by at least 1, also when the call then fails half-way; not when the call is refused by the checks it makes before it
+ *   touches anything: a NULL argument, a range out of bounds, a missing store, a refused mpcgpu_set_pair_order list, overlapping
+ *   shards of mpcgpu_store_import_part): mpcgpu_set_hmm, mpcgpu_set_seqs, mpcgpu_set_seqs_registry, mpcgpu_set_mega, an accepted
+ *   mpcgpu_set_pair_order (the order the context already has included: it drops shard and store), mpcgpu_calc_posteriors,
+ *   mpcgpu_build_store, mpcgpu_store_import, mpcgpu_store_import_part, mpcgpu_values_import, mpcgpu_cons_iter, mpcgpu_cons_commit,
+ *   mpcgpu_cons_commit_range, the list stages mpcgpu_align_pairs and mpcgpu_align_msas and mpcgpu_post_scores (they take the
+ *   scratch and invalidate the all-pairs store), and mpcgpu_group_set_hmm, _set_seqs, _set_mega, _calc_posteriors, _cons_iter on
+ *   every context of the group (they are made of the calls above).
+ *   LEAVES IT: mpcgpu_store_epoch itself, mpcgpu_last_error, mpcgpu_version, mpcgpu_pair_count, mpcgpu_pair_position,
+ *   mpcgpu_plan_partition and mpcgpu_plan_store_segments (no context), mpcgpu_shard_info, mpcgpu_shard_entries, mpcgpu_shard_export,
+ *   mpcgpu_store_complete (the same values in records of every sequence), mpcgpu_values_info, mpcgpu_values_slice,
+ *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
+ *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
+ *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_coop_info, mpcgpu_store_info,
+ *   mpcgpu_relax_info, mpcgpu_synchronize, and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
+ * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
+ * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
+int mpcgpu_store_epoch(mpcgpu_ctx *ctx, uint64_t *epoch);
+
 /* ---- pair order of a block-partitioned multi-GPU run -------------------------------
  * MPCFlat::InitPairs (mpcflat.cpp:139-159) enumerates the pairs row-major, and a contiguous range of that order holds pairs
  * (X, Y) with Y anywhere behind X: a rank that owns such a range needs the sparse matrices of nearly every sequence for

@@ -114,6 +114,9 @@ struct mpcgpu_ctx {
 	hipStream_t stream = nullptr;
 	hipDeviceProp_t prop;
 	std::string err;
+	// mpcgpu_store_epoch: moves in every call that replaces or invalidates tables, sequences, pair order, shard, store or committed
+	// values, once the call is past the checks that refuse it untouched (so a call that fails half-way has moved it); never in a reader
+	uint64_t epoch = 0;
 
 	// HMM (row 0)
 	bool have_hmm = false;
@@ -731,6 +734,14 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	delete c;
 }
 
+int mpcgpu_store_epoch(mpcgpu_ctx *c, uint64_t *epoch)
+{
+	if (!c) return 1;
+	if (!epoch) return fail(c, "mpcgpu_store_epoch: NULL argument");
+	*epoch = c->epoch;
+	return 0;
+}
+
 int mpcgpu_synchronize(mpcgpu_ctx *c)
 {
 	if (!c) return 1;
@@ -744,6 +755,7 @@ int mpcgpu_set_hmm(mpcgpu_ctx *c, const float start[5], const float trans[25], c
 {
 	if (!c) return 1;
 	if (!start || !trans || !match || !ins) return fail(c, "mpcgpu_set_hmm: NULL table");
+	++c->epoch;
 	memcpy(c->start, start, sizeof(c->start));
 	memcpy(c->trans, trans, sizeof(c->trans));
 	c->match256.assign(match, match + 65536);
@@ -770,6 +782,7 @@ static int set_seqs_impl(mpcgpu_ctx *c, uint32_t n, const uint8_t *const *seqs, 
 	if (n < 2) return fail(c, "mpcgpu_set_seqs: need at least 2 sequences (got %u)", n);
 	if (with_pairs && (u64)n * n > 0xffffffffull) return fail(c, "mpcgpu_set_seqs: too many sequences (%u)", n);
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	c->have_shard = c->have_store = false;
 	c->have_mega = false;
 	c->n = n;
@@ -852,6 +865,7 @@ int mpcgpu_set_pair_order(mpcgpu_ctx *c, uint32_t nrects, const uint32_t *rects)
 	HIPCHK(c, hipSetDevice(c->device));
 	const u32 n = c->n;
 	if (c->order_rects.size() == 4 * (size_t)nrects && (nrects == 0 || !memcmp(c->order_rects.data(), rects, 16 * (size_t)nrects))) {
+		++c->epoch;
 		c->have_shard = c->have_store = false;
 		c->partial = false;
 		return 0; // the order the context already has (mpcgpu_set_seqs leaves InitPairs order)
@@ -887,6 +901,7 @@ int mpcgpu_set_pair_order(mpcgpu_ctx *c, uint32_t nrects, const uint32_t *rects)
 		for (u64 q = 0; q < c->npairs; ++q) e2p[(u64)px[q] * n - ((u64)px[q] * (px[q] + 1)) / 2 + (py[q] - px[q] - 1)] = (u32)q;
 	}
 	// accepted: from here on the context takes the new order
+	++c->epoch;
 	c->have_shard = c->have_store = false;
 	c->partial = false;
 	c->order_rects.assign(rects, rects + 4 * (size_t)nrects);
@@ -922,6 +937,7 @@ int mpcgpu_set_mega(mpcgpu_ctx *c, uint32_t nfeat, const uint32_t *alpha, const 
 	if (!c) return 1;
 	if (c->n == 0) return fail(c, "mpcgpu_set_mega: call mpcgpu_set_seqs first");
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	c->have_shard = c->have_store = false;
 	c->have_mega = false;
 	if (nfeat == 0) return 0; // back to byte-sequence emissions

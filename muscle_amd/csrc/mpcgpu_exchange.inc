@@ -51,6 +51,7 @@ int mpcgpu_store_import_part(mpcgpu_ctx *c, uint32_t nshards, const uint64_t *k0
 		}
 	}
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	c->have_store = false;
 	c->tiles_k0 = c->tiles_k1 = ~0ull;
 	const u32 n = c->n;
@@ -228,6 +229,7 @@ int mpcgpu_values_import(mpcgpu_ctx *c, uint64_t first, uint64_t count, const vo
 	if (!c->have_store) return fail(c, "mpcgpu_values_import: no store");
 	if (count > c->total_entries || first > c->total_entries - count) return fail(c, "mpcgpu_values_import: range out of bounds");
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	if (count)
 		HIPCHK(c, hipMemcpyAsync(c->d_vnext.as<float>() + first, dev_src, count * 4, hipMemcpyDeviceToDevice, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -243,6 +245,7 @@ int mpcgpu_cons_iter(mpcgpu_ctx *c, uint64_t k0, uint64_t k1)
 		return fail(c, "mpcgpu_cons_iter: [%llu,%llu) is outside the range [%llu,%llu) this partial store was imported for (mpcgpu_store_import_part)",
 			(u64)k0, (u64)k1, (u64)c->own_k0, (u64)c->own_k1);
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	const u64 cnt = c->h_vbase[k1] - c->h_vbase[k0];
 	c->work_entry_z = cnt * c->n;
 	if (cnt == 0) return 0;
@@ -284,6 +287,7 @@ int mpcgpu_cons_commit_range(mpcgpu_ctx *c, uint64_t first, uint64_t count)
 	if (!c->have_store) return fail(c, "mpcgpu_cons_commit: no store");
 	if (count > c->total_entries || first > c->total_entries - count) return fail(c, "mpcgpu_cons_commit_range: range out of bounds");
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	if (count == 0) return 0;
 	StoreParams sp;
 	fill_store_params(c, sp);

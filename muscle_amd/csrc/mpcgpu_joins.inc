@@ -78,6 +78,7 @@ int mpcgpu_post_scores(mpcgpu_ctx *c, uint32_t LX, uint32_t LY, uint32_t ncand, 
 	if (!c->have_hmm) return fail(c, "mpcgpu_post_scores: set_hmm first (expf variant)");
 	if (LX == 0 || LY == 0 || LX > MPC_KEY_COL_MASK_LONG || LY > MPC_KEY_COL_MASK_LONG) return fail(c, "mpcgpu_post_scores: bad shape %u x %u", LX, LY);
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	const u32 capc = std::max<u32>(ncand, 1);
 	std::vector<u64> cand(capc, 0);
 	const u32 long_min = LX > 1023u ? LX : 0xffffffffu; // 22-bit column keys unless the rows need more than 10 bits
@@ -586,6 +587,7 @@ int mpcgpu_align_msas(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, cons
 	if (npairs == 0 || C1 == 0 || C2 == 0) return fail(c, "mpcgpu_align_msas: empty input");
 	for (u32 q = 0; q < npairs; ++q)
 		if (seq1[q] >= c->n || seq2[q] >= c->n) return fail(c, "mpcgpu_align_msas: sequence index out of range in pair %u", q);
+	++c->epoch;
 	// ---- stage A on the listed pairs (X = the MSA1 sequence, Y = the MSA2 sequence: calcpost.cpp:4-36)
 	if (stage_a(c, npairs, seq1, seq2)) return 1;
 	if (ea_out) memcpy(ea_out, c->sh_ea.data(), (size_t)npairs * 4);
@@ -820,6 +822,7 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 			return fail(c, "mpcgpu_align_pairs: pair %u is too long for a dense posterior: LX=%u, LY=%u, LX*LY*5 + 100 exceeds INT_MAX = %d", q, LX, LY, INT_MAX);
 	}
 	HIPCHK(c, hipSetDevice(c->device));
+	++c->epoch;
 	if (npairs >= 1 && npairs <= 64 && env_int("MPCGPU_PAIRS_SMALL", 1)) {
 		const int rc = align_pairs_small(c, npairs, seq1, seq2, path_stride, paths, pathlens, scores, ea);
 		if (rc != 2) return rc;

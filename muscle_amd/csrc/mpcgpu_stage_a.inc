@@ -729,6 +729,7 @@ int mpcgpu_calc_posteriors(mpcgpu_ctx *c, uint64_t k0, uint64_t k1)
 	if (!c) return 1;
 	if (c->n == 0) return fail(c, "mpcgpu_calc_posteriors: call mpcgpu_set_seqs first");
 	if (k0 > k1 || k1 > c->npairs) return fail(c, "mpcgpu_calc_posteriors: bad pair range [%llu,%llu)", (u64)k0, (u64)k1);
+	++c->epoch;
 	const int rc = stage_a(c, k1 - k0, c->h_pair_x.data() + k0, c->h_pair_y.data() + k0);
 	c->shard_is_list = false;
 	c->sh_k0 = k0; c->sh_k1 = k1;
