@@ -109,8 +109,8 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_store_complete (the same values in records of every sequence), mpcgpu_values_info, mpcgpu_values_slice,
  *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
  *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
- *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_coop_info, mpcgpu_store_info,
- *   mpcgpu_relax_info, mpcgpu_synchronize, and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
+ *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_coop_info, mpcgpu_post_info,
+ *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
  * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
 int mpcgpu_store_epoch(mpcgpu_ctx *ctx, uint64_t *epoch);
@@ -232,7 +232,10 @@ int mpcgpu_get_sparse_range(mpcgpu_ctx *ctx, uint64_t k0, uint64_t k1, uint32_t 
 /* The finishing kernels on one caller-supplied candidate list (cells (rows[q], cols[q]) with log-space Score scores[q] >=
  * MIN_SPARSE_SCORE, any order, no duplicates): the expf half of CalcPostFlat (calcposteriorflat.cpp:16-22),
  * MySparseMx::FromPost (mysparsemx.cpp:115-152) and CalcAlnScoreFlat / EA (calcalnscoreflat.cpp:4-32,
- * calcposteriorflat.cpp:89) for ONE pair of lengths LX, LY. kernel: 0 = row-list kernel, 1 = general (sort) kernel;
+ * calcposteriorflat.cpp:89) for ONE pair of lengths LX, LY. kernel: 0 = row-list kernel (post_rows_kernel), 1 = general (sort)
+ * kernel (post_kernel), 2 = the workgroup-per-pair kernel (post_wide_kernel: radix sort, row-start table, EA over the whole
+ * workgroup; MPCGPU_POSTW_LDS = entries it sorts in LDS and floats of an LDS DP row, 0 = everything through its global slots);
+ * any other value is refused.
  * batch: cells of a row per EA pass (64; smaller values exercise the multi-pass path). offsets[LX+1] / values (8 bytes per
  * kept entry, capacity ncand) may be NULL. A unit-test reach into inputs the pair-HMM itself never produces. */
 int mpcgpu_post_scores(mpcgpu_ctx *ctx, uint32_t LX, uint32_t LY, uint32_t ncand, const uint32_t *rows,
@@ -381,6 +384,16 @@ int mpcgpu_stage_a_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint64_t *chained_pair
  * (also when unset, until the rule has been measured on a device), 1 when a launch has fewer row-block pairs than the chip has wave
  * slots for them, 2..16 that many waves, always (clamped to the waves of a workgroup the chip keeps resident). */
 int mpcgpu_stage_a_coop_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint32_t *waves_per_pair);
+/* How the last finishing launch on this context ran (the kernels behind the sweeps: the expf half of CalcPostFlat,
+ * calcposteriorflat.cpp:16-22; MySparseMx::FromPost, mysparsemx.cpp:115-152; CalcAlnScoreFlat, calcalnscoreflat.cpp:4-32; EA,
+ * calcposteriorflat.cpp:89), whichever call made it: mpcgpu_calc_posteriors, a pair-list stage (its last batch) or
+ * mpcgpu_post_scores. out[0] the kernel: 0 = post_rows_kernel (row lists in LDS), 1 = post_kernel (one wavefront per pair, bitonic
+ * sorts), 2 = post_wide_kernel (a workgroup per pair, radix sort); out[1] threads per workgroup; out[2] pairs the launch finished;
+ * out[3] radix passes of the row-major sort of the pair with the most candidates (kernel 2; 0 for kernels 0 and 1). All 0 before the
+ * first such launch. Same records, same EA bits whichever kernel ran. MPCGPU_POST_WIDE: 0 = never post_wide_kernel, 1 = always (also
+ * for lists that fit the row-list kernel; mpcgpu_align_pairs then builds its dense posteriors from the raw candidate lists, as for
+ * a list that does not fit), unset = post_kernel for what the row-list kernel does not take. */
+int mpcgpu_post_info(mpcgpu_ctx *ctx, uint64_t out[4]);
 /* Sizes of the current store, for the measurement's lower bounds (bench.py: min_bytes_per_launch): out[0] bytes of the row-indexed
  * block records, out[1] of the window records (0: not built), out[2] of the packed matrices of all pairs, out[3] stored posteriors
  * of all pairs, out[4] of the pairs this context relaxes, out[5] sequences whose records the store holds (all of them unless the

@@ -19,7 +19,7 @@ SYMBOLS = [
     "mpcgpu_set_seqs", "mpcgpu_set_mega", "mpcgpu_pair_count", "mpcgpu_calc_posteriors", "mpcgpu_build_store",
     "mpcgpu_shard_info", "mpcgpu_shard_export", "mpcgpu_store_import", "mpcgpu_values_info", "mpcgpu_values_slice", "mpcgpu_values_export", "mpcgpu_values_import",
     "mpcgpu_cons_iter", "mpcgpu_cons_commit", "mpcgpu_cons_commit_range", "mpcgpu_get_ea", "mpcgpu_get_nnz", "mpcgpu_get_sparse",
-    "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_stage_a_coop_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
+    "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_stage_a_coop_info", "mpcgpu_post_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
     "mpcgpu_work_get", "mpcgpu_synchronize", "mpcgpu_relax_info", "mpcgpu_shard_entries",
     "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch", "mpcgpu_store_epoch",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
@@ -97,6 +97,7 @@ def load(lib_path=None):
     L.mpcgpu_work_get.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mpcgpu_stage_a_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mpcgpu_stage_a_coop_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
+    L.mpcgpu_post_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_synchronize.argtypes = [vp]
     L.mpcgpu_relax_info.argtypes = [vp, C.c_char_p, u32, C.POINTER(i32)]
     L.mpcgpu_group_create.argtypes = [C.POINTER(vp), u32, vp]
@@ -439,7 +440,8 @@ class MpcGpu:
         return out
 
     def post_scores(self, LX, LY, rows, cols, scores, kernel=0, batch=64):
-        """finishing kernels on one candidate list -> (ea, offsets, values) (include/mpcgpu.h: mpcgpu_post_scores)"""
+        """finishing kernels on one candidate list -> (ea, offsets, values) (include/mpcgpu.h: mpcgpu_post_scores); kernel: 0 row-list,
+        1 sort, 2 wide (a workgroup per pair), passed through unchanged"""
         rows, cols = np.ascontiguousarray(rows, np.uint32), np.ascontiguousarray(cols, np.uint32)
         scores = np.ascontiguousarray(scores, np.float32)
         ea, nnz = C.c_float(), C.c_uint32()
@@ -557,6 +559,13 @@ class MpcGpu:
         a, w = C.c_uint64(0), C.c_uint32(0)
         self._ck(self.L.mpcgpu_stage_a_coop_info(self.h, C.byref(a), C.byref(w)))
         return a.value, w.value
+
+    def post_info(self):
+        """(kernel, threads per workgroup, pairs, radix passes) of the last finishing launch on this context: kernel 0 = row-list,
+        1 = sort, 2 = wide; the passes are those of the pair with the most candidates (0 for kernels 0 and 1)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.L.mpcgpu_post_info(self.h, out))
+        return tuple(int(x) for x in out)
 
     def timers_reset(self):
         self._ck(self.L.mpcgpu_timers_reset(self.h))

@@ -11,6 +11,7 @@
 #include "kernels_fbc.h"
 #include "kernels_fbcoop.h"
 #include "kernels_post.h"
+#include "kernels_postw.h"
 #include "kernels_store.h"
 #include "kernels_relaxv.h"
 #include "kernels_relaxb.h"
@@ -219,6 +220,11 @@ struct mpcgpu_ctx {
 	u64 sa_b0 = 0, sa_B = 0;  // the last stage-A batch: first pair, pairs; candidate capacity, finishing kernel, key layout
 	u32 sa_capc = 0, sa_long_min = 0;
 	bool sa_post_rows = false;
+	// mpcgpu_post_info: the last finishing launch — kernel (0 row-list, 1 sort, 2 wide), threads per workgroup, pairs, and for the
+	// wide kernel its workgroups (each leaves (candidates << 8 | radix passes) of its largest list in d_pw_info)
+	u32 pi_kernel = 0, pi_threads = 0, pi_grid = 0;
+	u64 pi_pairs = 0;
+	DevBuf d_pw_rs, d_pw_info; // post_wide_kernel: row starts per resident workgroup; the words above
 	std::vector<u32> list_x, list_y; // the pairs of the last list stage
 	// mpcgpu_align_pairs runs its list in chunks (and halves a chunk that stage A had to split): the caller's WHOLE list and the
 	// index of the first pair of the chunk the last stage A ran on — mpcgpu_get_list_sparse(q) indexes the caller's list
@@ -723,6 +729,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->h_aln_res.release();
 	c->h_ap.release();
 	c->d_ap_off.release(); c->d_aln_bnd.release();
+	c->d_pw_rs.release(); c->d_pw_info.release();
 	c->d_chain_first.release(); c->d_chain_cnt.release();
 	c->d_bx_n.release(); c->d_by_n.release(); c->d_order_n.release(); c->d_chain_first_n.release(); c->d_chain_cnt_n.release();
 	c->d_rects.release(); c->d_need.release(); c->d_exp_klist.release(); c->d_exp_valbase.release();
@@ -1076,6 +1083,21 @@ int mpcgpu_stage_a_coop_info(mpcgpu_ctx *c, uint64_t *pairs, uint32_t *waves_per
 	if (!c) return 1;
 	if (pairs) *pairs = c->sa_coop_pairs;
 	if (waves_per_pair) *waves_per_pair = c->sa_coop_pairs ? c->sa_coop_waves : 0;
+	return 0;
+}
+
+int mpcgpu_post_info(mpcgpu_ctx *c, uint64_t out[4])
+{
+	if (!c) return 1;
+	if (!out) return fail(c, "mpcgpu_post_info: NULL argument");
+	out[0] = c->pi_kernel; out[1] = c->pi_threads; out[2] = c->pi_pairs; out[3] = 0;
+	if (c->pi_kernel == 2 && c->pi_grid) {
+		HIPCHK(c, hipSetDevice(c->device));
+		std::vector<u64> best(c->pi_grid, 0);
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(best.data(), c->d_pw_info.p, (size_t)c->pi_grid * 8, hipMemcpyDeviceToHost));
+		out[3] = *std::max_element(best.begin(), best.end()) & 0xffu;
+	}
 	return 0;
 }
 

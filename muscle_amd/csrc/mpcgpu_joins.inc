@@ -77,6 +77,7 @@ int mpcgpu_post_scores(mpcgpu_ctx *c, uint32_t LX, uint32_t LY, uint32_t ncand, 
 	if (!c) return 1;
 	if (!c->have_hmm) return fail(c, "mpcgpu_post_scores: set_hmm first (expf variant)");
 	if (LX == 0 || LY == 0 || LX > MPC_KEY_COL_MASK_LONG || LY > MPC_KEY_COL_MASK_LONG) return fail(c, "mpcgpu_post_scores: bad shape %u x %u", LX, LY);
+	if (kernel < 0 || kernel > 2) return fail(c, "mpcgpu_post_scores: kernel %d (0 = post_rows_kernel, 1 = post_kernel, 2 = post_wide_kernel)", kernel);
 	HIPCHK(c, hipSetDevice(c->device));
 	++c->epoch;
 	const u32 capc = std::max<u32>(ncand, 1);
@@ -103,11 +104,14 @@ int mpcgpu_post_scores(mpcgpu_ctx *c, uint32_t LX, uint32_t LY, uint32_t ncand, 
 			if (!post_rows_fits(LX, LY, 1)) { rc = fail(c, "mpcgpu_post_scores: %u x %u does not fit the row-list kernel", LX, LY); break; }
 			if (d_sort.ensure((u64)capc * 8 + 8) != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: out of device memory"); break; }
 			if (launch_post_rows(c, g, io, 1024, batch, 1, d_sort, false)) { rc = 1; break; }
+		} else if (kernel == 2) {
+			if (launch_post_wide(c, g, io, 1, false)) { rc = 1; break; }
 		} else {
 			PostParams pp;
 			const size_t psmem = fill_post(c, g, io, 1024, pp);
 			if (d_sort.ensure(pp.sort_stride * 8) != hipSuccess || d_srow.ensure(pp.srow_stride * 4) != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: out of device memory"); break; }
 			pp.sort_scratch = d_sort.as<u64>(); pp.srow_scratch = d_srow.as<float>();
+			post_info_set(c, 1, 64, 1, 1);
 			MPC_LAUNCH(post_kernel, 1, 64, psmem, c->stream, pp);
 		}
 		if (hipGetLastError() != hipSuccess) { rc = fail(c, "mpcgpu_post_scores: launch failed"); break; }

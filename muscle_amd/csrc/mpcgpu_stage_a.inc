@@ -468,6 +468,9 @@ static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &
 // and flags: the batch's device buffers (stage_a), page-locked memory for the outputs (align_pairs_small), buffers of its own (mpcgpu_post_scores)
 struct PostIO { const u32 *pair_x, *pair_y, *seq_len; u64 *cand; const u32 *cand_cnt; u32 *res, *nnz; float *ea; u32 *flags; u32 count; };
 
+// what mpcgpu_post_info reports: every finishing launch states its kernel (0 row-list, 1 sort, 2 wide), workgroup and pairs
+static void post_info_set(mpcgpu_ctx *c, u32 kernel, u32 threads, u32 grid, u64 pairs) { c->pi_kernel = kernel; c->pi_threads = threads; c->pi_grid = grid; c->pi_pairs = pairs; }
+
 // post_rows_kernel over io.count pairs that post_rows_fits(). sort_cap: entries of the LDS list of a pair's candidates; batch: cells of a row per
 // EA pass (stage_a passes MPCGPU_POST_SORT_CAP and MPCGPU_POST_BATCH, the others ignore the knobs). grid = 0: a persistent grid, as many workgroups
 // as are resident; else a workgroup per pair. scratch: a slot per workgroup for lists longer than sort_cap. timed = false: not in the launch counters.
@@ -499,6 +502,7 @@ static int launch_post_rows(mpcgpu_ctx *c, const StageAGeom &g, const PostIO &io
 	pr.res = io.res; pr.res_stride = g.res_stride();
 	pr.nnz = io.nnz; pr.ea = io.ea; pr.flags = io.flags;
 	pr.count = io.count; pr.long_min = g.long_min;
+	post_info_set(c, 0, 64, grid, io.count);
 	TimedSpan sp;
 	if (timed && span_begin(c, 1, &sp)) return 1;
 	MPC_LAUNCH(post_rows_kernel, grid, 64, smem, c->stream, pr);
@@ -524,12 +528,64 @@ static size_t fill_post(const mpcgpu_ctx *c, const StageAGeom &g, const PostIO &
 	return (size_t)pp.sort_cap * 8 + (size_t)pp.srow_cap * 2 * 4;
 }
 
+// MPCGPU_POST_WIDE: 0 = never post_wide_kernel, 1 = always (also lists that fit the row-list kernel), unset = the rule: a batch that
+// post_rows_fits() rejects goes to the wide kernel when kPostWideDefault says so. The rule may choose the wide kernel only where it
+// has been MEASURED no slower than post_kernel on each of 1 x 12 200^2, 300 x 20 000, 300 x 60 000, 6 000 x 60 000, 64 x 13 000^2
+// (DESIGN.md 1a). Measured so far: 70 against 342 ms, 13 against 150 ms and 89 against 413 ms of finishing time for the first, second
+// and last; the two widest have no figure for post_kernel yet, so the default stays post_kernel and the wide kernel is opt-in.
+static const int kPostWideDefault = 0;
+static int post_wide_env() { return env_int("MPCGPU_POST_WIDE", -1); }
+
+// post_wide_kernel (kernels_postw.h) over io.count pairs: a workgroup of MPC_POSTW_THREADS per pair. grid = 0: a persistent grid, as
+// many workgroups as are resident. Per workgroup, in context-owned buffers: two key slots of capc entries (lists beyond the LDS
+// buffers), LXmax + 1 row starts, two DP rows of LYmax + 1 floats (pairs wider than the LDS rows), one word for mpcgpu_post_info.
+// MPCGPU_POSTW_LDS (tests): entries sorted in LDS and floats of an LDS DP row at most; 0 = everything through the global slots.
+static int launch_post_wide(mpcgpu_ctx *c, const StageAGeom &g, const PostIO &io, u32 grid, bool timed)
+{
+	const u32 T = MPC_POSTW_THREADS;
+	const int lds_env = env_int("MPCGPU_POSTW_LDS", -1);
+	PostWideParams pw;
+	pw.pair_x = io.pair_x; pw.pair_y = io.pair_y; pw.seq_len = io.seq_len;
+	pw.cand = io.cand; pw.capc = g.capc; pw.cand_cnt = io.cand_cnt;
+	pw.use_fma = c->use_fma;
+	// 4096 entries in each of the two key buffers (64 KB) and 4096 floats in each DP row (32 KB) beside 41 KB of tables: 137 KB, one
+	// workgroup of 16 waves per CU either way
+	pw.lds_cap = std::min<u32>(g.capc, lds_env >= 0 ? std::min<u32>((u32)lds_env, 4096u) : 4096u);
+	pw.srow_cap = std::min<u32>(g.LYmax + 1, lds_env >= 0 ? std::min<u32>((u32)lds_env, 4096u) : 4096u);
+	const size_t smem = mpc_postw_smem(T, pw.lds_cap, pw.srow_cap);
+	ensure_dyn_smem((const void *)post_wide_kernel, smem);
+	if (!grid) {
+		int pocc = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pocc, (const void *)post_wide_kernel, (int)T, smem) != hipSuccess || pocc < 1) pocc = 1;
+		grid = (u32)std::min<u64>(io.count, (u64)c->prop.multiProcessorCount * (u32)pocc);
+	}
+	pw.key_stride = g.capc; pw.rs_stride = (u64)g.LXmax + 1; pw.srow_stride = 2 * ((u64)g.LYmax + 1);
+	HIPCHK(c, c->d_sort_scratch.ensure(g.capc > pw.lds_cap ? (u64)grid * 2 * pw.key_stride * 8 : 8));
+	HIPCHK(c, c->d_pw_rs.ensure((u64)grid * pw.rs_stride * 4));
+	HIPCHK(c, c->d_srow_scratch.ensure(g.LYmax + 1 > pw.srow_cap ? (u64)grid * pw.srow_stride * 4 : 8));
+	HIPCHK(c, c->d_pw_info.ensure((u64)grid * 8));
+	pw.key_scratch = c->d_sort_scratch.as<u64>(); pw.rs_scratch = c->d_pw_rs.as<u32>(); pw.srow_scratch = c->d_srow_scratch.as<float>();
+	pw.info = c->d_pw_info.as<u64>();
+	pw.res = io.res; pw.res_stride = g.res_stride();
+	pw.nnz = io.nnz; pw.ea = io.ea; pw.flags = io.flags;
+	pw.count = io.count; pw.long_min = g.long_min;
+	if (trace_on()) { fprintf(stderr, "[mpcgpu] post wide: %u threads per pair, lists of %u candidates and rows of %u floats in LDS, lds=%zu B grid=%u\n", T, pw.lds_cap, pw.srow_cap, smem, grid); fflush(stderr); }
+	post_info_set(c, 2, T, grid, io.count);
+	TimedSpan sp;
+	if (timed && span_begin(c, 1, &sp)) return 1;
+	MPC_LAUNCH(post_wide_kernel, grid, T, smem, c->stream, pw);
+	HIPCHK(c, hipGetLastError());
+	return timed ? span_end(c, &sp) : 0;
+}
+
 // The finishing kernel of the current batch (its index arrays are the current set: c->d_bx, c->d_by), and the event its sizes wait for.
-static int launch_post_batch(mpcgpu_ctx *c, const StageAGeom &g, bool post_rows, u32 sort_cap, u64 B)
+static int launch_post_batch(mpcgpu_ctx *c, const StageAGeom &g, bool post_rows, bool post_wide, u32 sort_cap, u64 B)
 {
 	const PostIO io = {c->d_bx.as<u32>(), c->d_by.as<u32>(), c->d_seq_len.as<u32>(), c->d_cand.as<u64>(), c->d_cand_cnt.as<u32>(), c->d_res.as<u32>(), c->d_nnz.as<u32>(), c->d_ea.as<float>(), c->d_flags.as<u32>(), (u32)B};
 	if (post_rows) {
 		if (launch_post_rows(c, g, io, sort_cap, (u32)std::max(env_int("MPCGPU_POST_BATCH", 64), 1), 0, c->d_sort_scratch, true)) return 1;
+	} else if (post_wide) {
+		if (launch_post_wide(c, g, io, 0, true)) return 1;
 	} else {
 		PostParams pp;
 		const size_t psmem = fill_post(c, g, io, sort_cap, pp);
@@ -542,6 +598,7 @@ static int launch_post_batch(mpcgpu_ctx *c, const StageAGeom &g, bool post_rows,
 		HIPCHK(c, c->d_sort_scratch.ensure(pp.sort_stride > pp.sort_cap ? (u64)pgrid * pp.sort_stride * 8 : 8));
 		HIPCHK(c, c->d_srow_scratch.ensure(g.LYmax + 1 > pp.srow_cap ? (u64)pgrid * pp.srow_stride * 4 : 8));
 		pp.sort_scratch = c->d_sort_scratch.as<u64>(); pp.srow_scratch = c->d_srow_scratch.as<float>();
+		post_info_set(c, 1, 64, pgrid, B);
 		TimedSpan sp;
 		if (span_begin(c, 1, &sp)) return 1;
 		MPC_LAUNCH(post_kernel, pgrid, 64, psmem, c->stream, pp);
@@ -646,7 +703,13 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	// batch of 125 000 pairs at L~400: 512 entries 16.9 ms, 768: 12.3, 896: 11.9, 1024: 11.7, 1280: 12.7, 1408 (holds every
 	// pair): 14.0, 1664: 15.8)
 	const u32 sort_cap = (u32)std::max(env_int("MPCGPU_POST_SORT_CAP", 1024), 2);
-	const bool post_rows = !(post_mode && !strcmp(post_mode, "sort")) && post_rows_fits(g.LXmax, g.LYmax, sort_cap);
+	const bool post_sort = post_mode && !strcmp(post_mode, "sort");
+	const int wide_env = post_wide_env();
+	const bool fits = post_rows_fits(g.LXmax, g.LYmax, sort_cap);
+	const bool post_rows = wide_env != 1 && !post_sort && fits;
+	// the wide kernel: forced (MPCGPU_POST_WIDE=1, whatever else is set), or by the rule for a batch that does not FIT the row-list
+	// kernel (MPCGPU_POST=sort keeps asking for post_kernel)
+	const bool post_wide = wide_env == 1 || (wide_env < 0 && kPostWideDefault && !post_sort && !fits);
 	const bool host_trace = trace_host(); // diagnostics: host wall time between the device phases of a batch
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double lap_t[6] = {0, 0, 0, 0, 0, 0}, t_prev = host_trace ? now() : 0.0;
@@ -669,7 +732,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	lap(0);
 	while (done < np) {
 		const u64 B = cur.B;
-		if (launch_post_batch(c, g, post_rows, sort_cap, B)) return 1;
+		if (launch_post_batch(c, g, post_rows, post_wide, sort_cap, B)) return 1;
 		lap(1);
 		// ---- the next batch: prepared on the host and its sweeps queued while the device runs this one
 		nxt.valid = false;
