@@ -109,7 +109,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_store_complete (the same values in records of every sequence), mpcgpu_values_info, mpcgpu_values_slice,
  *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
  *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
- *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_coop_info, mpcgpu_post_info,
+ *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
  *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
  * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
@@ -384,6 +384,13 @@ int mpcgpu_stage_a_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint64_t *chained_pair
  * (also when unset, until the rule has been measured on a device), 1 when a launch has fewer row-block pairs than the chip has wave
  * slots for them, 2..16 that many waves, always (clamped to the waves of a workgroup the chip keeps resident). */
 int mpcgpu_stage_a_coop_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint32_t *waves_per_pair);
+/* How many pairs of the last stage A were FINISHED inside the sweeps: a wavefront of fb_chain_post_kernel (kernels_fbc.h) that has swept
+ * a chain backward runs the row-list finishing code (what post_rows_kernel runs) for the chain's pairs before it takes the next chain,
+ * and the finishing launch of the batch is left with the other pairs. bins: bit H set = the chains of the bin of H rows per lane (rows
+ * of the row sequence / 64, rounded up) were finished that way. Either pointer may be NULL. Same records, same EA bits. MPCGPU_FB_POST_FUSE: 0 and unset = never,
+ * 1 = wherever the workgroup with its finishing slices fits a CU, 2 = where it is as often resident as the plain chain kernel and uses no
+ * scratch memory. */
+int mpcgpu_stage_a_fuse_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint32_t *bins);
 /* How the last finishing launch on this context ran (the kernels behind the sweeps: the expf half of CalcPostFlat,
  * calcposteriorflat.cpp:16-22; MySparseMx::FromPost, mysparsemx.cpp:115-152; CalcAlnScoreFlat, calcalnscoreflat.cpp:4-32; EA,
  * calcposteriorflat.cpp:89), whichever call made it: mpcgpu_calc_posteriors, a pair-list stage (its last batch) or

@@ -23,6 +23,7 @@
 // suites run every all-pairs set through both kernels, MPCGPU_FB_CHAIN=0 selects fb_kernel alone).
 #pragma once
 #include "kernels_fb.h"
+#include "kernels_post.h"
 
 #define MPC_CHAIN_MAX 16 // pairs per chain
 #define MPC_CHAIN_TAB_WORDS 8
@@ -34,8 +35,32 @@ struct FbChainParams {
 	const u32 *chain_cnt;   // per chain: members (1 .. MPC_CHAIN_MAX), all with the same pair_x
 };
 
-template <int H>
-__global__ void __launch_bounds__(256, (H == 8) ? 4 : 1) fb_chain_kernel(FbChainParams cp)
+// ---- finishing a chain's pairs in place (fb_chain_post_kernel): what mpc_post_rows_pair (kernels_post.h) needs beyond the sweeps.
+// A wave that has swept its chain backward finishes the chain's pairs itself before it takes the next chain: the finishing work is a
+// chain of dependent LDS trips that mostly waits, and here it waits beside three other waves of its SIMD whose sweeps
+// keep the VALU issuing. Every wave has a slice of dynamic LDS of its own behind the chain tables: the three per-position arrays
+// (lx_cap + 2 * ly_cap words) and a list of sort_cap entries; longer lists go through the wave's slot of sort_scratch.
+struct FbChainPost {
+	u32 lx_cap, ly_cap; // words: rows + 2, columns + 2 of the longest sequences
+	u32 sort_cap;       // entries of the per-wave LDS list
+	u32 wave_lds;       // bytes of a wave's slice (a multiple of 8)
+	u32 batch;          // PostRowsParams::batch
+	int use_fma;
+	u64 *sort_scratch;  // sort_stride entries per wave of the grid
+	u64 sort_stride;
+	u32 *res;
+	u64 res_stride;
+	u32 *nnz;
+	float *ea;
+	u32 *flags;
+};
+struct FbChainPostParams { FbChainParams c; FbChainPost post; };
+#ifndef MPC_DEVICE_FENCE
+#define MPC_DEVICE_FENCE() ((void)0) // the emulator: lanes meet at the wave rendezvous that follows
+#endif
+
+template <int H, bool POST>
+__device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbChainPost *pp)
 {
 	const FbParams &p = cp.f;
 	MPC_DYN_SMEM(smem_raw);
@@ -343,5 +368,38 @@ __global__ void __launch_bounds__(256, (H == 8) ? 4 : 1) fb_chain_kernel(FbChain
 		}
 		if (t == 0)
 			p.cand_cnt[pidA] = ncA;
+		if (POST) {
+			// The lists and counts this wave has just stored are read back by the same wave, by other lanes than wrote them. A release /
+			// acquire fence at device scope stands between: the wave waits until every store of the sweep has been acknowledged by the
+			// L2 (vmcnt 0, write-back of what the scope asks for) and its later loads do not use lines cached before that point. No other
+			// wave reads or writes these lists until the kernel has ended, so nothing beyond this wave's own program order is needed.
+			MPC_DEVICE_FENCE();
+			MPC_WAVE_LDS_ORDER();
+			u32 *s_rend = (u32 *)((unsigned char *)(s_tab_all + waves_per_block * (MPC_CHAIN_MAX * MPC_CHAIN_TAB_WORDS)) + (size_t)wave * pp->wave_lds);
+			u32 *s_cend = s_rend + pp->lx_cap;
+			float *s_pm = (float *)(s_cend + pp->ly_cap);
+			u64 *s_sorted = (u64 *)((unsigned char *)s_rend + ((((size_t)pp->lx_cap + 2 * (size_t)pp->ly_cap) * 4 + 7) & ~(size_t)7));
+			for (int k = 0; k < C; ++k) {
+				const u32 pid = tabw(k, 2);
+				const u32 c = mpc_wave_first(p.cand_cnt[pid]);
+				u64 *sorted = (c <= pp->sort_cap) ? s_sorted : (pp->sort_scratch + (u64)slot * pp->sort_stride);
+				mpc_post_rows_pair<false>(t, (u32)LX, tabw(k, 0), MPC_KEY_ROW_SHIFT, p.cand + (u64)pid * p.capc, c, p.capc, sorted,
+					pp->res + (u64)pid * pp->res_stride, pp->nnz + pid, pp->ea + pid, pp->flags + pid, pp->use_fma, pp->batch, s_rend, s_cend, s_pm);
+			}
+		}
 	}
+}
+
+template <int H>
+__global__ void __launch_bounds__(256, (H == 8) ? 4 : 1) fb_chain_kernel(FbChainParams cp)
+{
+	fb_chain_body<H, false>(cp, nullptr);
+}
+
+// the same sweeps, and every chain's pairs finished by the wave that swept them (see FbChainPost). Up to 8 rows per lane the sweeps fit 128
+// registers (4 waves per SIMD) and the finishing code is held to that too: left alone the allocator spends 161 at H = 7 on it.
+template <int H>
+__global__ void __launch_bounds__(256, (H <= 8) ? 4 : 1) fb_chain_post_kernel(FbChainPostParams cp)
+{
+	fb_chain_body<H, true>(cp.c, &cp.post);
 }

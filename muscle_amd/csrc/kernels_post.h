@@ -242,9 +242,258 @@ struct PostRowsParams {
 	u32 *flags;
 	u32 count;
 	u32 long_min; // as in PostParams
+	const u32 *sel; // the pairs to finish (count entries), or NULL: pairs 0 .. count-1 (the others were finished inside fb_chain_post_kernel)
 };
 
-// phase clock of post_rows_kernel (workgroup 0, lane 0 only)
+// Between two phases of a pair: what the lanes wrote (LDS, the record, the list) is read by other lanes next. WG: the wave is the whole
+// workgroup (post_rows_kernel) and a workgroup barrier does it. Otherwise (the wave finishes its chain inside fb_chain_post_kernel,
+// beside waves that are anywhere in their sweeps — a workgroup barrier would wait for them forever) the same point is wave-local: the
+// wave's LDS and memory instructions execute in order, the fence makes it wait for its own stores (vmcnt/lgkmcnt 0, what the barrier's
+// fence does too; a CU's vector cache is coherent for the waves of that CU), and the compiler moves nothing across.
+template <bool WG> __device__ __forceinline__ void mpc_post_sync()
+{
+	if (WG) __syncthreads();
+	else { MPC_WAVE_FENCE(); MPC_WAVE_LDS_ORDER(); }
+}
+
+// One pair by one wave (lane t): candidates cand[0 .. c) -> record, nnz, EA, flag. sorted: room for c entries (LDS or a slot in memory);
+// s_rend: LX + 1 words, s_cend and s_pm: LY + 1 words each, in LDS.
+template <bool WG>
+__device__ __forceinline__ void mpc_post_rows_pair(const int t, const u32 LX, const u32 LY, const u32 kshift, u64 *cand, const u32 c, const u32 capc,
+	u64 *sorted, u32 *rec, u32 *nnz_out, float *ea_out, u32 *flags_out, const int use_fma, const u32 batch, u32 *s_rend, u32 *s_cend, float *s_pm)
+{
+	if (c > capc) { // overflow: reported to the host, which retries with a larger capacity
+		if (t == 0) { *flags_out = 1u; *nnz_out = 0; *ea_out = 0.0f; }
+		return;
+	}
+	if (t == 0) *flags_out = 0u;
+	for (u32 q = t; q <= LX; q += 64) s_rend[q] = 0;
+	for (u32 q = t; q <= LY; q += 64) { s_cend[q] = 0; s_pm[q] = 0.0f; }
+	for (u32 q = t; q < LX + LY; q += 64) rec[q] = 0;
+	mpc_post_sync<WG>();
+	// ---- probabilities (calcposteriorflat.cpp:16-22) and the row histogram
+	for (u32 q = t; q < c; q += 64) {
+		const u64 v = cand[q];
+		const float pr = mpc_score_to_prob(__uint_as_float((u32)v), use_fma);
+		cand[q] = (v & 0xffffffff00000000ull) | (u64)__float_as_uint(pr);
+		atomicAdd(&s_rend[(u32)(v >> (32 + kshift))], 1u);
+	}
+	mpc_post_sync<WG>();
+	// exclusive scan of the row counts (in place: s_rend[i] = first slot of row i)
+	{
+		u32 carry = 0;
+		for (u32 a0 = 0; a0 <= LX; a0 += 64) {
+			const u32 a = a0 + t;
+			const u32 v = (a <= LX) ? s_rend[a] : 0;
+			u32 incl = v;
+			for (int d = 1; d < 64; d <<= 1) {
+				const u32 o = __shfl_up(incl, d);
+				if (t >= d) incl += o;
+			}
+			if (a <= LX) s_rend[a] = carry + incl - v;
+			carry += __shfl(incl, 63);
+		}
+	}
+	mpc_post_sync<WG>();
+	// scatter through the per-row cursor: afterwards s_rend[i] = END of row i (start of row i+1)
+	for (u32 q = t; q < c; q += 64) {
+		const u64 v = cand[q];
+		const u32 at = atomicAdd(&s_rend[(u32)(v >> (32 + kshift))], 1u);
+		sorted[at] = ((v >> 32) & (u64)((1u << kshift) - 1u)) << 32 | (v & 0xffffffffull);
+	}
+	mpc_post_sync<WG>();
+	// columns ascending inside each row (a lane per row; rows hold a handful of cells)
+	for (u32 i = t; i < LX; i += 64) {
+		const u32 b = i ? s_rend[i - 1] : 0u, e = s_rend[i];
+		for (u32 x = b + 1; x < e; ++x) {
+			const u64 key = sorted[x];
+			u32 y = x;
+			while (y > b && sorted[y - 1] > key) { sorted[y] = sorted[y - 1]; --y; }
+			sorted[y] = key;
+		}
+	}
+	mpc_post_sync<WG>();
+	// ---- EA score. PM is kept explicitly only up to column cmax, the right-most column any row has updated so far; right of
+	// it S(i,.) is flat (nothing stored there has been reached yet), PM[j] == PM[cmax]. Stored cells hug the alignment
+	// path, so a row updates the few columns between its first cell and that frontier instead of all LY of them.
+	// The rows are a dependent chain (row i reads what row i-1 wrote), so what a row costs is the latency of what it has to
+	// wait for. Off the chain: the row ends (64 rows per LDS read, then v_readlane) and the row's cells (the next non-empty
+	// row's cells start where this row's end, so they are loaded one row ahead). On it: PM[col-1] of the cells -> add ->
+	// wave scan -> the update of the few columns up to the frontier. The arrays belong to this wave alone (it is the whole
+	// workgroup, or has a slice of its own in fb_chain_post_kernel) and LDS executes a wave's accesses in order, so a row's writes
+	// need no barrier before the next row's reads.
+	u32 cmax = 0; // wave-uniform
+	u64 nkey = c ? sorted[(u32)t < c ? (u32)t : c - 1u] : 0ull; // cells [b, b+64) of the next non-empty row
+	for (u32 i0 = 0; i0 < LX; i0 += 64) {
+		const u32 ri = i0 + (u32)t;
+		const u32 rend_v = s_rend[ri < LX ? ri : LX - 1u]; // lane l: end of row i0+l
+		u32 b = mpc_wave_first(i0 ? s_rend[i0 - 1u] : 0u);
+		const u32 nl = LX - i0 < 64u ? LX - i0 : 64u;
+		for (u32 rl = 0; rl < nl; ++rl) {
+			const u32 e = mpc_read_lane(rend_v, rl);
+			if (e == b) continue;
+			if (e - b > batch) {
+				// more than one batch of cells (rare): every B must still come from the previous row's PM, so they are
+				// formed first (s_cend is free until the sparsify step), then the batches update PM one after the other
+				for (u32 x = b + (u32)t; x < e; x += 64) {
+					const u64 key = sorted[x];
+					const u32 cc = (u32)(key >> 32);
+					s_cend[x - b] = __float_as_uint(s_pm[cc < cmax ? cc : cmax] + __uint_as_float((u32)key));
+				}
+				mpc_post_sync<WG>();
+				float vprev = 0.0f; // maximum over the cells of this row handled so far
+				for (u32 c0 = b; c0 < e; c0 += batch) {
+					const u32 me = c0 + (u32)t;
+					const bool have = me < e && (u32)t < batch;
+					const u64 key = have ? sorted[me] : 0ull;
+					const u32 col = (u32)(key >> 32);
+					const float val = have ? __uint_as_float(s_cend[me - b]) : 0.0f;
+					const float suffix = s_pm[cmax];
+					const float V = fmaxf(mpc_wave_scan_max_nonneg(val), vprev);
+					const u32 k = (e - c0 < batch) ? (e - c0) : batch;
+					const u32 last = mpc_read_lane(col, k - 1) + 1u;
+					const u32 hi = last > cmax ? last : cmax;
+					// from the first column behind the frontier at the latest: a batch that starts right of cmax + 1 leaves a
+					// gap (cmax, first cell] that becomes explicit with this row and has to hold the flat suffix S(i-1, cmax)
+					const u32 jb0 = mpc_wave_first(col) + 1u;
+					for (u32 j0 = jb0 < cmax + 1u ? jb0 : cmax + 1u; j0 <= hi; j0 += 64) {
+						const u32 j = j0 + (u32)t;
+						float cur = 0.0f;
+						for (u32 l = 0; l < k; ++l) {
+							const u32 cj = mpc_read_lane(col, l) + 1u;
+							const float vj = mpc_read_lane(V, l);
+							cur = (j >= cj) ? vj : cur;
+						}
+						if (j <= hi) s_pm[j] = fmaxf(j <= cmax ? s_pm[j] : suffix, cur);
+					}
+					cmax = hi;
+					vprev = mpc_read_lane(V, k - 1);
+					mpc_post_sync<WG>();
+				}
+				for (u32 x = b + (u32)t; x < e; x += 64) s_cend[x - b] = 0;
+				mpc_post_sync<WG>();
+				nkey = sorted[e + (u32)t < c ? e + (u32)t : c - 1u];
+				b = e;
+				continue;
+			}
+			const u32 k = e - b; // 1..64 cells, lane l holds cell l (columns ascending)
+			const bool have = (u32)t < k;
+			const u64 key = nkey;
+			nkey = sorted[e + (u32)t < c ? e + (u32)t : c - 1u]; // in flight while this row is computed
+			const u32 col = have ? (u32)(key >> 32) : 0u;
+			const u32 jfirst = mpc_wave_first(col) + 1u;
+			// B = S(i-1,j-1) + P with j = col+1 (calcalnscoreflat.cpp:20)
+			const float val = have ? s_pm[col < cmax ? col : cmax] + __uint_as_float((u32)key) : 0.0f;
+			const float suffix = s_pm[cmax]; // S(i-1, j) for every j >= cmax
+			const float V = mpc_wave_scan_max_nonneg(val); // running maximum in column order
+			const u32 last = mpc_read_lane(col, k - 1) + 1u; // right-most column the row's cells start at
+			const u32 hi = last > cmax ? last : cmax;        // explicit range after this row
+			// The update starts at the row's first cell or, when that lies beyond the frontier, right behind the frontier:
+			// the columns in between become explicit with this row (cmax = hi below) and must receive S(i-1, cmax) — left
+			// unwritten they would keep their initial 0.0f and later rows would read it as S(., j).
+			for (u32 j0 = jfirst < cmax + 1u ? jfirst : cmax + 1u; j0 <= hi; j0 += 64) {
+				const u32 j = j0 + (u32)t;
+				const float old = s_pm[j <= cmax ? j : cmax];
+				float cur = 0.0f;
+				for (u32 l = 0; l < k; ++l) { // cells ascend in column: the last one with col+1 <= j wins
+					const u32 cj = mpc_read_lane(col, l) + 1u;
+					const float vj = mpc_read_lane(V, l);
+					cur = (j >= cj) ? vj : cur;
+				}
+				if (j <= hi) s_pm[j] = fmaxf(j <= cmax ? old : suffix, cur); // max(X, Y-chain) of the recurrence
+			}
+			cmax = hi;
+			b = e;
+			MPC_WAVE_LDS_ORDER();
+		}
+	}
+	const float score = s_pm[LY < cmax ? LY : cmax];
+	const u32 mn = LX < LY ? LX : LY;
+	const float ea = score / (float)mn; // calcposteriorflat.cpp:89 (uint -> float, IEEE divide)
+	mpc_post_sync<WG>();
+	// ---- sparsify (mysparsemx.cpp:115-152): keep P >= 0.01f, row-major rank among the kept
+	u32 kept = 0;
+	for (u32 q0 = 0; q0 < c; q0 += 64) {
+		const u32 q = q0 + t;
+		const bool k = q < c && __uint_as_float((u32)sorted[q]) >= MPC_MIN_SPARSE_PROB;
+		kept += (u32)__popcll(__ballot(k));
+	}
+	const u32 nnz = kept;
+	u32 *rowcnt = rec, *colcnt = rec + LX;
+	u32 *ent = rec + LX + LY;
+	u32 *rowv = ent + 2 * (u64)nnz;
+	u32 *tperm = rowv + nnz;
+	// row of every sorted slot: slots of row i are [s_rend[i-1], s_rend[i])
+	u32 base = 0;
+	for (u32 i0 = 0; i0 < LX; i0 += 64) { // a lane per row writes that row's kept cells
+		const u32 i = i0 + (u32)t;
+		u32 mycnt = 0;
+		u32 b = 0, e = 0;
+		if (i < LX) {
+			b = i ? s_rend[i - 1] : 0u; e = s_rend[i];
+			for (u32 x = b; x < e; ++x) mycnt += (__uint_as_float((u32)sorted[x]) >= MPC_MIN_SPARSE_PROB) ? 1u : 0u;
+		}
+		u32 incl = mycnt;
+		for (int d = 1; d < 64; d <<= 1) {
+			const u32 o = __shfl_up(incl, d);
+			if (t >= d) incl += o;
+		}
+		u32 at = base + incl - mycnt;
+		if (i < LX) {
+			rowcnt[i] = mycnt;
+			for (u32 x = b; x < e; ++x) {
+				const u64 key = sorted[x];
+				if (__uint_as_float((u32)key) >= MPC_MIN_SPARSE_PROB) {
+					const u32 col = (u32)(key >> 32);
+					ent[2 * (u64)at] = (u32)key;
+					ent[2 * (u64)at + 1] = col;
+					rowv[at] = i;
+					atomicAdd(&s_cend[col], 1u);
+					++at;
+				}
+			}
+		}
+		base += __shfl(incl, 63);
+	}
+	mpc_post_sync<WG>();
+	// ---- column-major rank of every kept entry: counting sort on the column, rows ascending inside
+	for (u32 q = t; q < LY; q += 64) colcnt[q] = s_cend[q];
+	{
+		u32 carry = 0;
+		for (u32 a0 = 0; a0 <= LY; a0 += 64) {
+			const u32 a = a0 + t;
+			const u32 v = (a <= LY) ? s_cend[a] : 0;
+			u32 incl = v;
+			for (int d = 1; d < 64; d <<= 1) {
+				const u32 o = __shfl_up(incl, d);
+				if (t >= d) incl += o;
+			}
+			if (a <= LY) s_cend[a] = carry + incl - v;
+			carry += __shfl(incl, 63);
+		}
+	}
+	mpc_post_sync<WG>();
+	u32 *csorted = (u32 *)sorted; // entry ranks in column-major order (the row-sorted list is no longer needed)
+	mpc_post_sync<WG>();
+	for (u32 q = t; q < nnz; q += 64) {
+		const u32 at = atomicAdd(&s_cend[ent[2 * (u64)q + 1]], 1u);
+		csorted[at] = q; // entry rank (row-major); rows ascend with the rank
+	}
+	mpc_post_sync<WG>();
+	for (u32 j = t; j < LY; j += 64) { // ranks ascending inside each column = rows ascending
+		const u32 b = j ? s_cend[j - 1] : 0u, e = s_cend[j];
+		for (u32 x = b + 1; x < e; ++x) {
+			const u32 key = csorted[x];
+			u32 y = x;
+			while (y > b && csorted[y - 1] > key) { csorted[y] = csorted[y - 1]; --y; }
+			csorted[y] = key;
+		}
+	}
+	mpc_post_sync<WG>();
+	for (u32 q = t; q < nnz; q += 64) tperm[csorted[q]] = q;
+	if (t == 0) { *nnz_out = nnz; *ea_out = ea; }
+	mpc_post_sync<WG>();
+}
 
 __global__ void __launch_bounds__(64) post_rows_kernel(PostRowsParams p)
 {
@@ -255,242 +504,12 @@ __global__ void __launch_bounds__(64) post_rows_kernel(PostRowsParams p)
 	u64 *s_sorted = (u64 *)(smem_raw + ((((size_t)p.lx_cap + 2 * (size_t)p.ly_cap) * 4 + 7) & ~(size_t)7)); // sort_cap: (col << 32 | P bits), row-major
 	const int t = threadIdx.x;
 
-	for (u32 pid = blockIdx.x; pid < p.count; pid += gridDim.x) {
+	for (u32 k = blockIdx.x; k < p.count; k += gridDim.x) {
+		const u32 pid = p.sel ? p.sel[k] : k;
 		const u32 LX = p.seq_len[p.pair_x[pid]], LY = p.seq_len[p.pair_y[pid]];
-		const u32 kshift = mpc_key_shift(LX, p.long_min);
-		u32 *rec = p.res + (u64)pid * p.res_stride;
 		const u32 c = p.cand_cnt[pid];
-		if (c > p.capc) { // overflow: reported to the host, which retries with a larger capacity
-			if (t == 0) { p.flags[pid] = 1u; p.nnz[pid] = 0; p.ea[pid] = 0.0f; }
-			continue;
-		}
-		if (t == 0) p.flags[pid] = 0u;
-		u64 *cand = p.cand + (u64)pid * p.capc;
 		u64 *sorted = (c <= p.sort_cap) ? s_sorted : (p.sort_scratch + (u64)blockIdx.x * p.sort_stride);
-		for (u32 q = t; q <= LX; q += 64) s_rend[q] = 0;
-		for (u32 q = t; q <= LY; q += 64) { s_cend[q] = 0; s_pm[q] = 0.0f; }
-		for (u32 q = t; q < LX + LY; q += 64) rec[q] = 0;
-		__syncthreads();
-		// ---- probabilities (calcposteriorflat.cpp:16-22) and the row histogram
-		for (u32 q = t; q < c; q += 64) {
-			const u64 v = cand[q];
-			const float pr = mpc_score_to_prob(__uint_as_float((u32)v), p.use_fma);
-			cand[q] = (v & 0xffffffff00000000ull) | (u64)__float_as_uint(pr);
-			atomicAdd(&s_rend[(u32)(v >> (32 + kshift))], 1u);
-		}
-		__syncthreads();
-		// exclusive scan of the row counts (in place: s_rend[i] = first slot of row i)
-		{
-			u32 carry = 0;
-			for (u32 a0 = 0; a0 <= LX; a0 += 64) {
-				const u32 a = a0 + t;
-				const u32 v = (a <= LX) ? s_rend[a] : 0;
-				u32 incl = v;
-				for (int d = 1; d < 64; d <<= 1) {
-					const u32 o = __shfl_up(incl, d);
-					if (t >= d) incl += o;
-				}
-				if (a <= LX) s_rend[a] = carry + incl - v;
-				carry += __shfl(incl, 63);
-			}
-		}
-		__syncthreads();
-		// scatter through the per-row cursor: afterwards s_rend[i] = END of row i (start of row i+1)
-		for (u32 q = t; q < c; q += 64) {
-			const u64 v = cand[q];
-			const u32 at = atomicAdd(&s_rend[(u32)(v >> (32 + kshift))], 1u);
-			sorted[at] = ((v >> 32) & (u64)((1u << kshift) - 1u)) << 32 | (v & 0xffffffffull);
-		}
-		__syncthreads();
-		// columns ascending inside each row (a lane per row; rows hold a handful of cells)
-		for (u32 i = t; i < LX; i += 64) {
-			const u32 b = i ? s_rend[i - 1] : 0u, e = s_rend[i];
-			for (u32 x = b + 1; x < e; ++x) {
-				const u64 key = sorted[x];
-				u32 y = x;
-				while (y > b && sorted[y - 1] > key) { sorted[y] = sorted[y - 1]; --y; }
-				sorted[y] = key;
-			}
-		}
-		__syncthreads();
-		// ---- EA score. PM is kept explicitly only up to column cmax, the right-most column any row has updated so far; right of
-		// it S(i,.) is flat (nothing stored there has been reached yet), PM[j] == PM[cmax]. Stored cells hug the alignment
-		// path, so a row updates the few columns between its first cell and that frontier instead of all LY of them.
-		// The rows are a dependent chain (row i reads what row i-1 wrote), so what a row costs is the latency of what it has to
-		// wait for. Off the chain: the row ends (64 rows per LDS read, then v_readlane) and the row's cells (the next non-empty
-		// row's cells start where this row's end, so they are loaded one row ahead). On it: PM[col-1] of the cells -> add ->
-		// wave scan -> the update of the few columns up to the frontier. One wavefront is the whole workgroup and LDS executes a
-		// wave's accesses in order, so a row's writes need no barrier before the next row's reads.
-		u32 cmax = 0; // wave-uniform
-		u64 nkey = c ? sorted[(u32)t < c ? (u32)t : c - 1u] : 0ull; // cells [b, b+64) of the next non-empty row
-		for (u32 i0 = 0; i0 < LX; i0 += 64) {
-			const u32 ri = i0 + (u32)t;
-			const u32 rend_v = s_rend[ri < LX ? ri : LX - 1u]; // lane l: end of row i0+l
-			u32 b = mpc_wave_first(i0 ? s_rend[i0 - 1u] : 0u);
-			const u32 nl = LX - i0 < 64u ? LX - i0 : 64u;
-			for (u32 rl = 0; rl < nl; ++rl) {
-				const u32 e = mpc_read_lane(rend_v, rl);
-				if (e == b) continue;
-				if (e - b > p.batch) {
-					// more than one batch of cells (rare): every B must still come from the previous row's PM, so they are
-					// formed first (s_cend is free until the sparsify step), then the batches update PM one after the other
-					for (u32 x = b + (u32)t; x < e; x += 64) {
-						const u64 key = sorted[x];
-						const u32 cc = (u32)(key >> 32);
-						s_cend[x - b] = __float_as_uint(s_pm[cc < cmax ? cc : cmax] + __uint_as_float((u32)key));
-					}
-					__syncthreads();
-					float vprev = 0.0f; // maximum over the cells of this row handled so far
-					for (u32 c0 = b; c0 < e; c0 += p.batch) {
-						const u32 me = c0 + (u32)t;
-						const bool have = me < e && (u32)t < p.batch;
-						const u64 key = have ? sorted[me] : 0ull;
-						const u32 col = (u32)(key >> 32);
-						const float val = have ? __uint_as_float(s_cend[me - b]) : 0.0f;
-						const float suffix = s_pm[cmax];
-						const float V = fmaxf(mpc_wave_scan_max_nonneg(val), vprev);
-						const u32 k = (e - c0 < p.batch) ? (e - c0) : p.batch;
-						const u32 last = mpc_read_lane(col, k - 1) + 1u;
-						const u32 hi = last > cmax ? last : cmax;
-						// from the first column behind the frontier at the latest: a batch that starts right of cmax + 1 leaves a
-						// gap (cmax, first cell] that becomes explicit with this row and has to hold the flat suffix S(i-1, cmax)
-						const u32 jb0 = mpc_wave_first(col) + 1u;
-						for (u32 j0 = jb0 < cmax + 1u ? jb0 : cmax + 1u; j0 <= hi; j0 += 64) {
-							const u32 j = j0 + (u32)t;
-							float cur = 0.0f;
-							for (u32 l = 0; l < k; ++l) {
-								const u32 cj = mpc_read_lane(col, l) + 1u;
-								const float vj = mpc_read_lane(V, l);
-								cur = (j >= cj) ? vj : cur;
-							}
-							if (j <= hi) s_pm[j] = fmaxf(j <= cmax ? s_pm[j] : suffix, cur);
-						}
-						cmax = hi;
-						vprev = mpc_read_lane(V, k - 1);
-						__syncthreads();
-					}
-					for (u32 x = b + (u32)t; x < e; x += 64) s_cend[x - b] = 0;
-					__syncthreads();
-					nkey = sorted[e + (u32)t < c ? e + (u32)t : c - 1u];
-					b = e;
-					continue;
-				}
-				const u32 k = e - b; // 1..64 cells, lane l holds cell l (columns ascending)
-				const bool have = (u32)t < k;
-				const u64 key = nkey;
-				nkey = sorted[e + (u32)t < c ? e + (u32)t : c - 1u]; // in flight while this row is computed
-				const u32 col = have ? (u32)(key >> 32) : 0u;
-				const u32 jfirst = mpc_wave_first(col) + 1u;
-				// B = S(i-1,j-1) + P with j = col+1 (calcalnscoreflat.cpp:20)
-				const float val = have ? s_pm[col < cmax ? col : cmax] + __uint_as_float((u32)key) : 0.0f;
-				const float suffix = s_pm[cmax]; // S(i-1, j) for every j >= cmax
-				const float V = mpc_wave_scan_max_nonneg(val); // running maximum in column order
-				const u32 last = mpc_read_lane(col, k - 1) + 1u; // right-most column the row's cells start at
-				const u32 hi = last > cmax ? last : cmax;        // explicit range after this row
-				// The update starts at the row's first cell or, when that lies beyond the frontier, right behind the frontier:
-				// the columns in between become explicit with this row (cmax = hi below) and must receive S(i-1, cmax) — left
-				// unwritten they would keep their initial 0.0f and later rows would read it as S(., j).
-				for (u32 j0 = jfirst < cmax + 1u ? jfirst : cmax + 1u; j0 <= hi; j0 += 64) {
-					const u32 j = j0 + (u32)t;
-					const float old = s_pm[j <= cmax ? j : cmax];
-					float cur = 0.0f;
-					for (u32 l = 0; l < k; ++l) { // cells ascend in column: the last one with col+1 <= j wins
-						const u32 cj = mpc_read_lane(col, l) + 1u;
-						const float vj = mpc_read_lane(V, l);
-						cur = (j >= cj) ? vj : cur;
-					}
-					if (j <= hi) s_pm[j] = fmaxf(j <= cmax ? old : suffix, cur); // max(X, Y-chain) of the recurrence
-				}
-				cmax = hi;
-				b = e;
-				MPC_WAVE_LDS_ORDER();
-			}
-		}
-		const float score = s_pm[LY < cmax ? LY : cmax];
-		const u32 mn = LX < LY ? LX : LY;
-		const float ea = score / (float)mn; // calcposteriorflat.cpp:89 (uint -> float, IEEE divide)
-		__syncthreads();
-		// ---- sparsify (mysparsemx.cpp:115-152): keep P >= 0.01f, row-major rank among the kept
-		u32 kept = 0;
-		for (u32 q0 = 0; q0 < c; q0 += 64) {
-			const u32 q = q0 + t;
-			const bool k = q < c && __uint_as_float((u32)sorted[q]) >= MPC_MIN_SPARSE_PROB;
-			kept += (u32)__popcll(__ballot(k));
-		}
-		const u32 nnz = kept;
-		u32 *rowcnt = rec, *colcnt = rec + LX;
-		u32 *ent = rec + LX + LY;
-		u32 *rowv = ent + 2 * (u64)nnz;
-		u32 *tperm = rowv + nnz;
-		// row of every sorted slot: slots of row i are [s_rend[i-1], s_rend[i])
-		u32 base = 0;
-		for (u32 i0 = 0; i0 < LX; i0 += 64) { // a lane per row writes that row's kept cells
-			const u32 i = i0 + (u32)t;
-			u32 mycnt = 0;
-			u32 b = 0, e = 0;
-			if (i < LX) {
-				b = i ? s_rend[i - 1] : 0u; e = s_rend[i];
-				for (u32 x = b; x < e; ++x) mycnt += (__uint_as_float((u32)sorted[x]) >= MPC_MIN_SPARSE_PROB) ? 1u : 0u;
-			}
-			u32 incl = mycnt;
-			for (int d = 1; d < 64; d <<= 1) {
-				const u32 o = __shfl_up(incl, d);
-				if (t >= d) incl += o;
-			}
-			u32 at = base + incl - mycnt;
-			if (i < LX) {
-				rowcnt[i] = mycnt;
-				for (u32 x = b; x < e; ++x) {
-					const u64 key = sorted[x];
-					if (__uint_as_float((u32)key) >= MPC_MIN_SPARSE_PROB) {
-						const u32 col = (u32)(key >> 32);
-						ent[2 * (u64)at] = (u32)key;
-						ent[2 * (u64)at + 1] = col;
-						rowv[at] = i;
-						atomicAdd(&s_cend[col], 1u);
-						++at;
-					}
-				}
-			}
-			base += __shfl(incl, 63);
-		}
-		__syncthreads();
-		// ---- column-major rank of every kept entry: counting sort on the column, rows ascending inside
-		for (u32 q = t; q < LY; q += 64) colcnt[q] = s_cend[q];
-		{
-			u32 carry = 0;
-			for (u32 a0 = 0; a0 <= LY; a0 += 64) {
-				const u32 a = a0 + t;
-				const u32 v = (a <= LY) ? s_cend[a] : 0;
-				u32 incl = v;
-				for (int d = 1; d < 64; d <<= 1) {
-					const u32 o = __shfl_up(incl, d);
-					if (t >= d) incl += o;
-				}
-				if (a <= LY) s_cend[a] = carry + incl - v;
-				carry += __shfl(incl, 63);
-			}
-		}
-		__syncthreads();
-		u32 *csorted = (u32 *)sorted; // entry ranks in column-major order (the row-sorted list is no longer needed)
-		__syncthreads();
-		for (u32 q = t; q < nnz; q += 64) {
-			const u32 at = atomicAdd(&s_cend[ent[2 * (u64)q + 1]], 1u);
-			csorted[at] = q; // entry rank (row-major); rows ascend with the rank
-		}
-		__syncthreads();
-		for (u32 j = t; j < LY; j += 64) { // ranks ascending inside each column = rows ascending
-			const u32 b = j ? s_cend[j - 1] : 0u, e = s_cend[j];
-			for (u32 x = b + 1; x < e; ++x) {
-				const u32 key = csorted[x];
-				u32 y = x;
-				while (y > b && csorted[y - 1] > key) { csorted[y] = csorted[y - 1]; --y; }
-				csorted[y] = key;
-			}
-		}
-		__syncthreads();
-		for (u32 q = t; q < nnz; q += 64) tperm[csorted[q]] = q;
-		if (t == 0) { p.nnz[pid] = nnz; p.ea[pid] = ea; }
-		__syncthreads();
+		mpc_post_rows_pair<true>(t, LX, LY, mpc_key_shift(LX, p.long_min), p.cand + (u64)pid * p.capc, c, p.capc, sorted, p.res + (u64)pid * p.res_stride,
+			p.nnz + pid, p.ea + pid, p.flags + pid, p.use_fma, p.batch, s_rend, s_cend, s_pm);
 	}
 }

@@ -131,6 +131,8 @@ template <class T> __device__ __forceinline__ const __attribute__((address_space
 // orders this wave's earlier global stores before its later global loads (other lanes' data): s_waitcnt only,
 // the waves of a workgroup share the CU's L1
 #define MPC_WAVE_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
+// release + acquire at device scope: earlier stores are complete in the L2 before any later load is issued
+#define MPC_DEVICE_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent")
 // float -> u32, truncating, saturating (negative and NaN -> 0, >= 2^32 -> 0xffffffff): what v_cvt_u32_f32 does. The C cast is
 // undefined outside the range, so the instruction is named (plain asm: schedulable, no side effects).
 __device__ __forceinline__ unsigned mpc_cvt_u32_sat(float f) { unsigned r; asm("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(f)); return r; }

@@ -253,6 +253,11 @@ struct mpcgpu_ctx {
 	// stage A's batch pipeline (mpcgpu_stage_a.inc): the index arrays of the NEXT batch (its sweeps are queued while this batch's sizes
 	// are on their way to the host), the stream those sizes come back on and the event behind the finishing kernel
 	DevBuf d_bx_n, d_by_n, d_order_n, d_chain_first_n, d_chain_cnt_n;
+	// fb_chain_post_kernel (chains finished inside the sweeps): the pairs left to the finishing launch, of this batch and the next; the second
+	// set of records, sizes and flags that the next batch's sweeps write; the waves' slots for lists beyond their LDS list
+	DevBuf d_rest, d_rest_n, d_res_n, d_nnz_n, d_ea_n, d_flags_n, d_fuse_sort;
+	u64 sa_fused = 0; // last stage A: pairs finished inside the sweeps
+	u32 sa_fuse_bins = 0; // ... and the rows-per-lane bins they ran in (bit H)
 	hipStream_t stream2 = nullptr;
 	hipEvent_t ev_post = nullptr;
 	u64 sa_pairs = 0, sa_chained = 0, sa_chains = 0; // last stage A: pairs, pairs that ran in chains, chains
@@ -522,6 +527,68 @@ void launch_fbc_h(int H, const FbChainParams &p, u32 grid, u32 block, size_t sme
 	}
 }
 
+// fb_chain_post_kernel (kernels_fbc.h): the chain sweeps with every chain's pairs finished in place. smem includes the waves' finishing slices.
+template <int H> void launch_fbcp(const FbChainPostParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+{
+	auto kern = fb_chain_post_kernel<H>;
+	ensure_dyn_smem((const void *)kern, smem);
+	MPC_LAUNCH(kern, grid, block, smem, st, p);
+}
+
+// workgroups a CU keeps resident (0: such a workgroup does not fit)
+template <int H> int occ_fbcp(u32 block, size_t smem)
+{
+	int nb = 0;
+	ensure_dyn_smem((const void *)fb_chain_post_kernel<H>, smem);
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fb_chain_post_kernel<H>, (int)block, smem) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
+	return nb;
+}
+
+// does the instantiation keep values in scratch memory (the register allocator spilled)? The emulator has no registers to run out of.
+template <int H> bool fbcp_spills()
+{
+#ifdef MPC_EMU
+	return false;
+#else
+	hipFuncAttributes a;
+	if (hipFuncGetAttributes(&a, (const void *)fb_chain_post_kernel<H>) != hipSuccess) { (void)hipGetLastError(); return true; }
+	return a.localSizeBytes != 0;
+#endif
+}
+
+bool fbcp_spills_h(int H)
+{
+	switch (H) {
+#define MPC_CASE(h) case h: return fbcp_spills<h>();
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: return true;
+	}
+}
+
+int occ_fbcp_h(int H, u32 block, size_t smem)
+{
+	switch (H) {
+#define MPC_CASE(h) case h: return occ_fbcp<h>(block, smem);
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: return 0;
+	}
+}
+
+void launch_fbcp_h(int H, const FbChainPostParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+{
+	switch (H) {
+#define MPC_CASE(h) case h: launch_fbcp<h>(p, grid, block, smem, st); break;
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: break;
+	}
+}
+
 // shard buffer layout: [u64 npairs][u64 record_words_total][u32 nnz[np]][f32 ea[np]] pad to 8 | records
 u64 shard_header_bytes(u64 np) { return ((16 + np * 8 + 7) / 8) * 8; }
 u64 rec_words(u32 LX, u32 LY, u32 nnz) { return (u64)LX + LY + 4 * (u64)nnz; }
@@ -732,6 +799,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->d_pw_rs.release(); c->d_pw_info.release();
 	c->d_chain_first.release(); c->d_chain_cnt.release();
 	c->d_bx_n.release(); c->d_by_n.release(); c->d_order_n.release(); c->d_chain_first_n.release(); c->d_chain_cnt_n.release();
+	for (DevBuf *b : {&c->d_rest, &c->d_rest_n, &c->d_res_n, &c->d_nnz_n, &c->d_ea_n, &c->d_flags_n, &c->d_fuse_sort}) b->release();
 	c->d_rects.release(); c->d_need.release(); c->d_exp_klist.release(); c->d_exp_valbase.release();
 	c->d_tiles2.release();
 	c->pad_seg.release(); release_windows(c);
@@ -1075,6 +1143,14 @@ int mpcgpu_stage_a_info(mpcgpu_ctx *c, uint64_t *pairs, uint64_t *chained_pairs,
 	if (pairs) *pairs = c->sa_pairs;
 	if (chained_pairs) *chained_pairs = c->sa_chained;
 	if (chains) *chains = c->sa_chains;
+	return 0;
+}
+
+int mpcgpu_stage_a_fuse_info(mpcgpu_ctx *c, uint64_t *pairs, uint32_t *bins)
+{
+	if (!c) return 1;
+	if (pairs) *pairs = c->sa_fused;
+	if (bins) *bins = c->sa_fuse_bins;
 	return 0;
 }
 

@@ -78,6 +78,9 @@ struct BatchPrep {
 	u32 ccount[MPC_HMAX + 1];   // chains per rows-per-lane bin
 	u32 cvmax[MPC_HMAX + 1];    // longest virtual column axis of a bin's chains
 	u32 coop_pairs = 0, coop_waves = 0; // set by the launch: row-block pairs that went to fb_coop_kernel, and its waves per pair
+	// fused bins (ChainPlan::fuse): `rest` lists the pairs the sweeps do not finish, for the separate finishing launch
+	u64 fused = 0; // pairs the sweeps finish
+	std::vector<u32> rest;
 };
 
 // Chains: consecutive pairs of the list with the same row sequence (the all-pairs order is full of them), each with
@@ -87,7 +90,56 @@ struct ChainPlan {
 	bool on = false, grade = true; // grade = false: no shorter chains at the end of a launch (MPCGPU_FB_CHAIN_GRADE=0: tests)
 	u32 max = 0; size_t smem = 0;
 	u32 vcap[MPC_HMAX + 1] = {0}; // columns a chain of a rows-per-lane bin may have; 0: the bin takes no chains
+	// fb_chain_post_kernel (fuse_plan): the bins whose chains are finished inside the sweeps, the LDS list of a wave there, any bin at all
+	bool fuse[MPC_HMAX + 1] = {false}, fuse_any = false;
+	u32 fuse_sort_cap[MPC_HMAX + 1] = {0};
+	u32 post_batch = 64;
 };
+// bytes of the three per-position LDS arrays of the row-list finishing code
+static size_t post_rows_fixed_lds(const StageAGeom &g) { return ((((size_t)g.LXmax + 2 + 2 * ((size_t)g.LYmax + 2)) * 4 + 7) & ~(size_t)7); }
+static size_t fuse_smem(const ChainPlan &cp, const StageAGeom &g, u32 sort_cap) { return cp.smem + (size_t)SA_WAVES * (post_rows_fixed_lds(g) + 8 * (size_t)sort_cap); }
+
+// Unset is 0: at 7 rows per lane (1000 x L~400) the fused kernel does not fit the sweeps' 128 registers without scratch memory, and
+// neither that bin as fuse_plan now sizes it nor the bins that do fit have a device time on record (DESIGN.md 4.2: the one run of a
+// fused H = 7, 880 against 542 ms, was of an earlier form at half the residency).
+static const int kFbPostFuseDefault = 0;
+// MPCGPU_FB_POST_FUSE. Which bins of the chain kernel finish their pairs inside the sweeps (fb_chain_post_kernel). 2 (the rule): a bin is fused when
+// a workgroup with the waves' finishing slices — the per-position arrays and a list of at least 2 and at most min(capc, sort_cap) entries, as many
+// as fit — is as often resident on a CU as the plain chain kernel's is and the instantiation uses no scratch memory (at 6 to 8 rows per lane the
+// finishing code does not fit the 128 registers of the sweeps without spilling). 1: wherever the workgroup fits at all — with scratch memory,
+// and at a lower residency where even a list of 2 entries costs the chain kernel's. 0 (and unset): never. Fusing needs the row-list finishing code
+// (post_rows) and, with more than one batch, a second set of record buffers (the sweeps of batch b + 1 write records while those of
+// batch b wait for their pack): the list is fused only when that set — the records of a batch at most — takes no more than a quarter of the free memory.
+static int fuse_plan(mpcgpu_ctx *c, const StageAGeom &g, u64 np, u64 batch_budget, bool post_rows, u32 sort_cap, ChainPlan &cp)
+{
+	const int env = env_int("MPCGPU_FB_POST_FUSE", kFbPostFuseDefault);
+	cp.post_batch = (u32)std::min(std::max(env_int("MPCGPU_POST_BATCH", 64), 1), 64);
+	if (!cp.on || !post_rows || env == 0) return 0;
+	size_t freeb = 0, totb = 0;
+	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
+	const u64 owned = (u64)c->d_cand.cap + c->d_res.cap + c->d_res_n.cap + c->d_fm.cap;
+	const u64 second = std::min<u64>(np * g.res_stride() * 4, std::min<u64>(batch_budget, (u64)((freeb + owned) * 0.4)));
+	if (second > (freeb + c->d_res_n.cap) / 4) {
+		if (trace_on()) { fprintf(stderr, "[mpcgpu] fb chain post: not fused, a second set of records (%llu B) is more than a quarter of the free memory (%zu B)\n", second, freeb + c->d_res_n.cap); fflush(stderr); }
+		return 0;
+	}
+	const u32 top = std::max(std::min<u32>(g.capc, sort_cap), 2u);
+	for (u32 H = 1; H <= MPC_HMAX; ++H) {
+		if (!cp.vcap[H]) continue;
+		const int occ0 = occ_fbc_h((int)H, SA_BLOCK, cp.smem);
+		if (env != 1 && fbcp_spills_h((int)H)) continue; // held to the sweeps' registers, the finishing code spilled: not by the rule
+		const int occ2 = occ_fbcp_h((int)H, SA_BLOCK, fuse_smem(cp, g, 2));
+		const int need = occ2 >= occ0 ? occ0 : env == 1 ? 1 : occ0;
+		if (occ2 < need) continue;
+		u32 lo = 2, hi = top; // the largest list with which `need` workgroups stay resident
+		while (lo < hi) {
+			const u32 mid = lo + (hi - lo + 1) / 2;
+			if (occ_fbcp_h((int)H, SA_BLOCK, fuse_smem(cp, g, mid)) >= need) lo = mid; else hi = mid - 1;
+		}
+		cp.fuse[H] = true; cp.fuse_sort_cap[H] = lo; cp.fuse_any = true;
+	}
+	return 0;
+}
 static int chain_plan(mpcgpu_ctx *c, const StageAGeom &g, u64 planes_budget, ChainPlan &cp)
 {
 	cp.on = !g.mega && env_int("MPCGPU_FB_CHAIN", 1) != 0;
@@ -182,7 +234,7 @@ static int prepare_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &cp
 	size_t freeb = 0, totb = 0;
 	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
 	// the scratch of the previous batch (or of an overflow retry) is already owned and gets reused: count it as available
-	const u64 owned = (u64)c->d_cand.cap + c->d_res.cap + c->d_fm.cap;
+	const u64 owned = (u64)c->d_cand.cap + c->d_res.cap + c->d_res_n.cap + c->d_fm.cap;
 	// Fewer, larger batches save the tails of waves that finish alone. Round 5 (batch after batch): 16 GB = four batches at 1000 x L~400;
 	// 24 GB / 3 batches: fb 551 -> 545 ms, step 1832 -> 1822; 32 / 2: 541, 1840 — the first batch's host preparation was not covered
 	// by device work (profiles/r05a, r05c, r05d).
@@ -226,6 +278,15 @@ static int prepare_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &cp
 		P.chain_first.push_back((u32)at);
 		P.chain_cnt.push_back(ch.cnt);
 		for (u32 k = 0; k < ch.cnt; ++k) P.order[at++] = ch.q0 + k;
+	}
+	// what the separate finishing launch is left with when bins are fused: the pairs outside the chain kernel and the chains of the other bins
+	P.fused = 0; P.rest.clear();
+	if (cp.fuse_any) {
+		P.rest.assign(P.order.begin(), P.order.begin() + keys.size());
+		for (const Chain &ch : chains) {
+			if (cp.fuse[ch.H]) { P.fused += ch.cnt; continue; }
+			for (u32 k = 0; k < ch.cnt; ++k) P.rest.push_back(ch.q0 + k);
+		}
 	}
 	P.valid = true;
 	return 0;
@@ -406,7 +467,8 @@ static int launch_fb_bins(mpcgpu_ctx *c, const StageAGeom &g, FbParams fp, const
 }
 
 // ---- forward/backward, the chains of a batch (kernels_fbc.h): one launch per bin; order, first, cnt: the batch's arrays on the device
-static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &plan, const FbParams &fp, const BatchPrep &P, const u32 *order, const u32 *first, const u32 *cnts)
+// post: where a fused bin (plan.fuse) leaves records, sizes and flags; its waves' slots for lists beyond their LDS list are c->d_fuse_sort
+static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &plan, const FbParams &fp, const BatchPrep &P, const u32 *order, const u32 *first, const u32 *cnts, const FbChainPost &post)
 {
 	const u32 cus = (u32)c->prop.multiProcessorCount;
 	TimedSpan sp;
@@ -414,7 +476,9 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 	for (u32 H = 1; H <= MPC_HMAX; ++H) {
 		if (!P.ccount[H]) continue;
 		const u32 cnt = P.ccount[H];
-		const u32 occ = (u32)occ_fbc_h((int)H, SA_BLOCK, plan.smem);
+		const bool fuse = plan.fuse[H];
+		const size_t smem = fuse ? fuse_smem(plan, g, plan.fuse_sort_cap[H]) : plan.smem;
+		const u32 occ = (u32)std::max(fuse ? occ_fbcp_h((int)H, SA_BLOCK, smem) : occ_fbc_h((int)H, SA_BLOCK, plan.smem), 1);
 		const u32 grid = std::max(std::min<u32>((cnt + SA_WAVES - 1) / SA_WAVES, cus * occ), 1u);
 		const u64 fm_stride = (u64)(P.cvmax[H] + 64) * H * 64;
 		HIPCHK(c, c->d_fm.ensure((u64)grid * SA_WAVES * fm_stride * 4));
@@ -424,6 +488,7 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 			u64 members = 0;
 			for (u32 k = 0; k < cnt; ++k) members += P.chain_cnt[cpos + k];
 			fprintf(stderr, "[mpcgpu] fb chain members H=%u pairs=%llu capc=%u batch=%llu\n", H, members, g.capc, P.B);
+			if (fuse) fprintf(stderr, "[mpcgpu] fb chain post: H=%u finishes its %llu pairs in the sweeps, list of %u candidates in LDS, lds=%zu B per workgroup\n", H, members, plan.fuse_sort_cap[H], smem);
 			fflush(stderr);
 		}
 		FbChainParams cp;
@@ -432,8 +497,20 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 		cp.f.queue = c->d_queue.as<u32>() + (MPC_HMAX + 2) + H;
 		cp.f.fm_scratch = c->d_fm.as<float>(); cp.f.fm_stride = fm_stride;
 		cp.chain_first = first + cpos; cp.chain_cnt = cnts + cpos;
-		if (span_begin(c, 0, &sp)) return 1;
-		launch_fbc_h((int)H, cp, grid, SA_BLOCK, plan.smem, c->stream);
+		if (fuse) {
+			FbChainPostParams fpp;
+			fpp.c = cp; fpp.post = post;
+			fpp.post.sort_cap = plan.fuse_sort_cap[H];
+			fpp.post.wave_lds = (u32)(post_rows_fixed_lds(g) + 8 * (size_t)fpp.post.sort_cap);
+			fpp.post.sort_stride = g.capc;
+			HIPCHK(c, c->d_fuse_sort.ensure(g.capc > fpp.post.sort_cap ? (u64)grid * SA_WAVES * g.capc * 8 : 8));
+			fpp.post.sort_scratch = c->d_fuse_sort.as<u64>();
+			if (span_begin(c, 0, &sp)) return 1;
+			launch_fbcp_h((int)H, fpp, grid, SA_BLOCK, smem, c->stream);
+		} else {
+			if (span_begin(c, 0, &sp)) return 1;
+			launch_fbc_h((int)H, cp, grid, SA_BLOCK, plan.smem, c->stream);
+		}
 		HIPCHK(c, hipGetLastError());
 		if (span_end(c, &sp)) return 1;
 		cpos += cnt;
@@ -446,13 +523,24 @@ static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &
 {
 	DevBuf &dbx = into_next ? c->d_bx_n : c->d_bx, &dby = into_next ? c->d_by_n : c->d_by, &dord = into_next ? c->d_order_n : c->d_order;
 	DevBuf &dcf = into_next ? c->d_chain_first_n : c->d_chain_first, &dcc = into_next ? c->d_chain_cnt_n : c->d_chain_cnt;
+	// With fused bins the sweeps write records, sizes and flags: those of the next batch go to the second set (this batch's are still to be read)
+	const bool alt = into_next && plan.fuse_any;
+	DevBuf &dres = alt ? c->d_res_n : c->d_res, &dnnz = alt ? c->d_nnz_n : c->d_nnz, &dea = alt ? c->d_ea_n : c->d_ea, &dflags = alt ? c->d_flags_n : c->d_flags;
 	const u64 B = P.B;
 	if (upload(c, dbx, P.bx) || upload(c, dby, P.by) || upload(c, dord, P.order)) return 1;
 	if (!P.chain_first.empty() && (upload(c, dcf, P.chain_first) || upload(c, dcc, P.chain_cnt))) return 1;
+	if (plan.fuse_any && upload(c, into_next ? c->d_rest_n : c->d_rest, P.rest)) return 1;
 	if (ensure_pair_scratch(c, g, B)) return 1;
-	HIPCHK(c, c->d_nnz.ensure(B * 4));
-	HIPCHK(c, c->d_ea.ensure(B * 4));
-	HIPCHK(c, c->d_flags.ensure(B * 4));
+	HIPCHK(c, dres.ensure(B * g.res_stride() * 4));
+	HIPCHK(c, dnnz.ensure(B * 4));
+	HIPCHK(c, dea.ensure(B * 4));
+	HIPCHK(c, dflags.ensure(B * 4));
+	FbChainPost post;
+	post.lx_cap = g.LXmax + 2; post.ly_cap = g.LYmax + 2; post.sort_cap = 0; post.wave_lds = 0;
+	post.batch = plan.post_batch; post.use_fma = c->use_fma;
+	post.sort_scratch = nullptr; post.sort_stride = 0;
+	post.res = dres.as<u32>(); post.res_stride = g.res_stride();
+	post.nnz = dnnz.as<u32>(); post.ea = dea.as<float>(); post.flags = dflags.as<u32>();
 	FbParams fp;
 	fill_fb_params(c, fp, dbx.as<u32>(), dby.as<u32>(), g.capc, g.mega);
 	P.coop_pairs = P.coop_waves = 0;
@@ -461,12 +549,12 @@ static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &
 		for (u32 H = 1; H <= MPC_HMAX; ++H) first += P.hcount[H];
 		if (launch_fb_row_block_pairs(c, g, fp, dord.as<u32>() + first, P.hcount[MPC_HMAX + 1], planes_budget, P)) return 1;
 	}
-	return launch_fb_bins(c, g, fp, dord.as<u32>(), P.hcount, B) || launch_fb_chains(c, g, plan, fp, P, dord.as<u32>(), dcf.as<u32>(), dcc.as<u32>());
+	return launch_fb_bins(c, g, fp, dord.as<u32>(), P.hcount, B) || launch_fb_chains(c, g, plan, fp, P, dord.as<u32>(), dcf.as<u32>(), dcc.as<u32>(), post);
 }
 
 // ---- the finishing kernels (probabilities, sort, EA, sparsify). Where a launch finds its pairs and candidate lists and leaves records, sizes
 // and flags: the batch's device buffers (stage_a), page-locked memory for the outputs (align_pairs_small), buffers of its own (mpcgpu_post_scores)
-struct PostIO { const u32 *pair_x, *pair_y, *seq_len; u64 *cand; const u32 *cand_cnt; u32 *res, *nnz; float *ea; u32 *flags; u32 count; };
+struct PostIO { const u32 *pair_x, *pair_y, *seq_len; u64 *cand; const u32 *cand_cnt; u32 *res, *nnz; float *ea; u32 *flags; u32 count; const u32 *sel = nullptr; u32 nsel = 0; }; // sel: the nsel pairs (of count) to finish, NULL: all
 
 // what mpcgpu_post_info reports: every finishing launch states its kernel (0 row-list, 1 sort, 2 wide), workgroup and pairs
 static void post_info_set(mpcgpu_ctx *c, u32 kernel, u32 threads, u32 grid, u64 pairs) { c->pi_kernel = kernel; c->pi_threads = threads; c->pi_grid = grid; c->pi_pairs = pairs; }
@@ -494,15 +582,16 @@ static int launch_post_rows(mpcgpu_ctx *c, const StageAGeom &g, const PostIO &io
 		// (measured, per batch of 125 000 pairs: 15 248 B of LDS, 10 workgroups per CU reported: 12.7 ms; 15 760 B, still 10
 		// reported: 22.5 ms; 17 296 B, 9 reported: 14.1 ms — 64-thread workgroups stop fitting at ~152 KB per CU, not 160)
 		pocc = std::max(1, std::min(pocc, (int)((152 * 1024) / smem)));
-		grid = (u32)std::min<u64>(io.count, (u64)c->prop.multiProcessorCount * (u32)pocc);
+		// (behind fused sweeps the launch finishes what they left, which may be nothing: it stays, as the place in the stream the sizes wait for)
+		grid = (u32)std::max<u64>(std::min<u64>(io.sel ? io.nsel : io.count, (u64)c->prop.multiProcessorCount * (u32)pocc), 1);
 		if (trace_on()) { fprintf(stderr, "[mpcgpu] post rows: list of %u candidates in LDS, lds=%zu B blocks/CU=%d grid=%u\n", pr.sort_cap, smem, pocc, grid); fflush(stderr); }
 	}
 	HIPCHK(c, scratch.ensure(g.capc > pr.sort_cap ? (u64)grid * pr.sort_stride * 8 : 8));
 	pr.sort_scratch = scratch.as<u64>();
 	pr.res = io.res; pr.res_stride = g.res_stride();
 	pr.nnz = io.nnz; pr.ea = io.ea; pr.flags = io.flags;
-	pr.count = io.count; pr.long_min = g.long_min;
-	post_info_set(c, 0, 64, grid, io.count);
+	pr.count = io.sel ? io.nsel : io.count; pr.long_min = g.long_min; pr.sel = io.sel;
+	post_info_set(c, 0, 64, grid, pr.count);
 	TimedSpan sp;
 	if (timed && span_begin(c, 1, &sp)) return 1;
 	MPC_LAUNCH(post_rows_kernel, grid, 64, smem, c->stream, pr);
@@ -579,9 +668,11 @@ static int launch_post_wide(mpcgpu_ctx *c, const StageAGeom &g, const PostIO &io
 }
 
 // The finishing kernel of the current batch (its index arrays are the current set: c->d_bx, c->d_by), and the event its sizes wait for.
-static int launch_post_batch(mpcgpu_ctx *c, const StageAGeom &g, bool post_rows, bool post_wide, u32 sort_cap, u64 B)
+// rest: with fused bins (ChainPlan::fuse_any), the pairs the sweeps left (c->d_rest); NULL: every pair of the batch
+static int launch_post_batch(mpcgpu_ctx *c, const StageAGeom &g, bool post_rows, bool post_wide, u32 sort_cap, u64 B, const std::vector<u32> *rest)
 {
-	const PostIO io = {c->d_bx.as<u32>(), c->d_by.as<u32>(), c->d_seq_len.as<u32>(), c->d_cand.as<u64>(), c->d_cand_cnt.as<u32>(), c->d_res.as<u32>(), c->d_nnz.as<u32>(), c->d_ea.as<float>(), c->d_flags.as<u32>(), (u32)B};
+	PostIO io = {c->d_bx.as<u32>(), c->d_by.as<u32>(), c->d_seq_len.as<u32>(), c->d_cand.as<u64>(), c->d_cand_cnt.as<u32>(), c->d_res.as<u32>(), c->d_nnz.as<u32>(), c->d_ea.as<float>(), c->d_flags.as<u32>(), (u32)B};
+	if (rest) { io.sel = c->d_rest.as<u32>(); io.nsel = (u32)rest->size(); }
 	if (post_rows) {
 		if (launch_post_rows(c, g, io, sort_cap, (u32)std::max(env_int("MPCGPU_POST_BATCH", 64), 1), 0, c->d_sort_scratch, true)) return 1;
 	} else if (post_wide) {
@@ -697,6 +788,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	const ScratchBudget budget = scratch_budget();
 	ChainPlan chain;
 	if (chain_plan(c, g, budget.planes, chain)) return 1;
+	c->sa_fused = 0; c->sa_fuse_bins = 0;
 	// the row-list finishing kernel when the list fits it; MPCGPU_POST=sort forces the general one
 	const char *post_mode = getenv("MPCGPU_POST");
 	// LDS list of a pair's candidates (larger lists cost resident waves, pairs that exceed it sort through HBM scratch; per
@@ -710,6 +802,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	// the wide kernel: forced (MPCGPU_POST_WIDE=1, whatever else is set), or by the rule for a batch that does not FIT the row-list
 	// kernel (MPCGPU_POST=sort keeps asking for post_kernel)
 	const bool post_wide = wide_env == 1 || (wide_env < 0 && kPostWideDefault && !post_sort && !fits);
+	if (fuse_plan(c, g, np, budget.batch, post_rows, sort_cap, chain)) return 1;
 	const bool host_trace = trace_host(); // diagnostics: host wall time between the device phases of a batch
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double lap_t[6] = {0, 0, 0, 0, 0, 0}, t_prev = host_trace ? now() : 0.0;
@@ -732,7 +825,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	lap(0);
 	while (done < np) {
 		const u64 B = cur.B;
-		if (launch_post_batch(c, g, post_rows, post_wide, sort_cap, B)) return 1;
+		if (launch_post_batch(c, g, post_rows, post_wide, sort_cap, B, chain.fuse_any ? &cur.rest : nullptr)) return 1;
 		lap(1);
 		// ---- the next batch: prepared on the host and its sweeps queued while the device runs this one
 		nxt.valid = false;
@@ -761,11 +854,17 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 		c->sa_b0 = done; c->sa_B = B; c->sa_capc = g.capc; c->sa_post_rows = post_rows; c->sa_long_min = g.long_min;
 		done += B;
 		for (u32 c2 : cur.chain_cnt) if (c2 >= 2) { c->sa_chains += 1; c->sa_chained += c2; }
+		c->sa_fused += cur.fused;
+		for (u32 H = 1; H <= MPC_HMAX; ++H) if (chain.fuse[H] && cur.ccount[H]) c->sa_fuse_bins |= 1u << H;
 		if (cur.coop_pairs) { c->sa_coop_pairs += cur.coop_pairs; c->sa_coop_waves = cur.coop_waves; }
 		std::swap(cur, nxt);
 		if (cur.valid) { // the next batch's index arrays become the current set
 			std::swap(c->d_bx, c->d_bx_n); std::swap(c->d_by, c->d_by_n); std::swap(c->d_order, c->d_order_n);
 			std::swap(c->d_chain_first, c->d_chain_first_n); std::swap(c->d_chain_cnt, c->d_chain_cnt_n);
+			if (chain.fuse_any) {
+				std::swap(c->d_rest, c->d_rest_n); std::swap(c->d_res, c->d_res_n);
+				std::swap(c->d_nnz, c->d_nnz_n); std::swap(c->d_ea, c->d_ea_n); std::swap(c->d_flags, c->d_flags_n);
+			}
 		}
 		lap(4);
 	}
