@@ -257,6 +257,7 @@ int mpcgpu_cons_iter(mpcgpu_ctx *c, uint64_t k0, uint64_t k1)
 			if (r == 2 && c->win_ok) {
 				// no band fits with the Y rows as windows (one wide row can be most of the LDS): the same tiles with the Y rows as block
 				// lists, i.e. the two-list walk; the window records are dropped
+				if (trace_on()) fprintf(stderr, "[mpcgpu] relax: no band tile fits with window records: windows dropped, the walk is cut\n");
 				release_windows(c);
 				{ const size_t at = c->store_desc.find(" + window records"); if (at != std::string::npos) c->store_desc.erase(at); }
 				c->btiles_k0 = c->btiles_k1 = ~0ull;
@@ -264,6 +265,7 @@ int mpcgpu_cons_iter(mpcgpu_ctx *c, uint64_t k0, uint64_t k1)
 				r = relax_band(c, sp, k0, k1);
 			}
 			if (r != 2) return r;
+			if (trace_on()) fprintf(stderr, "[mpcgpu] relax: no band tile fits: %s from here on\n", c->var_pairs_ok ? "whole-record tiles" : "CSR slabs");
 			c->band_ok = false; // this store's rows do not cut into band tiles that fit: whole-record tiles from here on
 		}
 		if (c->var_pairs_ok) return relax_var(c, sp, k0, k1); // (never a store in segments: build_var_store)

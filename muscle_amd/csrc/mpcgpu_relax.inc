@@ -246,6 +246,10 @@ static int choose_shape(const BandCut &bc, BandShape &s, std::vector<u32> &words
 			s = {a, b, got == 3 && kb ? std::min<u32>(kb * 64, g.cap_blocks) : half};
 			if (cut(bc, s.nx, s.ny, s.target, words, out)) return 1;
 		}
+		if (trace_on()) {
+			if (s.nx) fprintf(stderr, "[mpcgpu] band tiles forced: %ux%u, target %u blocks\n", s.nx, s.ny, s.target);
+			else fprintf(stderr, "[mpcgpu] band tiles: MPCGPU_RELAX_SHAPE=%s is not a shape, searching\n", sh);
+		}
 	}
 	if (!s.nx && n <= 64) { // route 2
 		// few sequences (the shrubs of -super7, the clusters of -super5): the 8 x 8 super-tiles with ALL their rows as one band
@@ -259,6 +263,8 @@ static int choose_shape(const BandCut &bc, BandShape &s, std::vector<u32> &words
 		if (eval_tiles(bc, w2, o2)) return 1;
 		bool ok = !w2.empty();
 		for (size_t t = 0; t + 3 < o2.size(); t += 4) ok = ok && o2[t] <= max_slots && o2[t + 1] <= half;
+		if (trace_on()) fprintf(stderr, "[mpcgpu] band tiles, %u sequences, one band per 8x8 super-tile: %zu tiles, %s\n", n, o2.size() / 4,
+			ok ? "taken" : "refused (a super-tile over the slots or the target)");
 		if (ok) { words.swap(w2); out.swap(o2); s = {8, 8, half}; }
 	}
 	if (!s.nx) { // route 3: 8x8 with two steps resident, taken at once where it fills the register slots
@@ -270,10 +276,12 @@ static int choose_shape(const BandCut &bc, BandShape &s, std::vector<u32> &words
 		if (trace_on()) fprintf(stderr, "[mpcgpu] band tiles 8x8, two steps resident: %llu tiles, fill %.2f, %.2f B/cell-step, %.0f %% within target\n",
 			(unsigned long long)tiles, fill, cells ? 16.0 * (double)est / (double)cells : 0.0, 100 * in_target);
 		if (!tiles) return 0;
-		if (fill >= 0.70 && in_target >= 0.90) s = {8, 8, half};
+		const char *why = "not taken, searching"; // (trace only)
+		if (fill >= 0.70 && in_target >= 0.90) { s = {8, 8, half}; why = "taken, the slots are filled"; }
 		// few cells (the shrubs of -super7: 32 sequences): nothing was cut — one band per super-tile — so no other shape or target
 		// gives fewer tile-steps, and the search below (20 more cuts) is skipped
-		else if (in_target >= 1.0 && tiles == with_cells) s = {8, 8, half};
+		else if (in_target >= 1.0 && tiles == with_cells) { s = {8, 8, half}; why = "taken, nothing was cut"; }
+		if (trace_on()) fprintf(stderr, "[mpcgpu] band tiles 8x8, two steps resident: %s\n", why);
 	}
 	if (s.nx) return 0;
 	// route 4: the priced search
@@ -368,6 +376,7 @@ static int fit_or_split(const BandCut &bc, std::vector<u32> &words, std::vector<
 			for (size_t q = 0; q < need.size(); ++q) out[4 * need[q] + 2] = exact[q]; // the bound becomes the exact worst step
 		}
 		std::vector<u32> next;
+		u64 by_band = 0, by_y = 0, by_x = 0, over_first = 0; // (trace only)
 		for (u32 t = 0; t < nt; ++t) {
 			const u32 *w = &words[(size_t)t * MPC_RB_TILE_WORDS];
 			if (out[4 * t + 3] == 0) continue; // no cell
@@ -381,7 +390,12 @@ static int fit_or_split(const BandCut &bc, std::vector<u32> &words, std::vector<
 			}
 			next.insert(next.end(), a, a + MPC_RB_TILE_WORDS);
 			next.insert(next.end(), b, b + MPC_RB_TILE_WORDS);
+			if (a[5] != w[5]) ++by_band; else if (a[3] != w[3]) ++by_y; else ++by_x;
+			if (out[4 * t] <= max_slots && w[6] > MPC_RB_MAXFIRST) ++over_first;
 		}
+		if (trace_on() && by_band + by_y + by_x)
+			fprintf(stderr, "[mpcgpu] band tiles: round %d halves %llu tiles by band, %llu by Y, %llu by X (%llu of them over the first-piece limit of %u blocks alone)\n",
+				round, (unsigned long long)by_band, (unsigned long long)by_y, (unsigned long long)by_x, (unsigned long long)over_first, (unsigned)MPC_RB_MAXFIRST);
 		words.swap(next);
 		if (eval_tiles(bc, words, out)) return 1;
 	}
@@ -471,6 +485,8 @@ static int cut_band_tiles(mpcgpu_ctx *c, const StoreParams &sp, const BandGeom &
 		okw.clear();
 		for (size_t t = 0; t < w2.size() / MPC_RB_TILE_WORDS; ++t)
 			if (o2[4 * t + 3]) okw.insert(okw.end(), w2.begin() + t * MPC_RB_TILE_WORDS, w2.begin() + (t + 1) * MPC_RB_TILE_WORDS);
+		if (trace_on()) fprintf(stderr, "[mpcgpu] band tiles: tail of %zu tiles on %u CUs: %llu cut in two by rows, %zu halves without a cell dropped\n",
+			w2.size() / MPC_RB_TILE_WORDS - (size_t)ntail_split, g.cus, (unsigned long long)ntail_split, (w2.size() - okw.size()) / MPC_RB_TILE_WORDS);
 	}
 	c->tiles_desc = describe_band_tiles(g, s, nsplit, okw.size() / MPC_RB_TILE_WORDS, o2);
 	c->h_btiles.swap(okw);
@@ -554,13 +570,19 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 		HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)kBandThreads, smem) != hipSuccess || occ < 1) occ = 1;
 		c->band_fn = fn; c->band_smem = smem; c->band_occ = occ;
+		if (trace_on()) fprintf(stderr, "[mpcgpu] relax band: LDS attribute and occupancy of the kernel asked at %zu B (%d per CU)\n", smem, occ);
 	}
 	const u32 grid = std::max(std::min<u32>(ntiles, g.cus * (u32)occ), 1u);
 	char kn[128];
 	snprintf(kn, sizeof(kn), "relax_band_kernel<%u, %u, 2, %d, %s%s%s>", kBandThreads, g.kernel_slots, diag, seg ? "MpcRbSegmented<" : "",
 		g.use_win ? (merge_cxx ? "MpcRbWinCxx" : "MpcRbWinAsm") : merge_cxx && !diag ? "MpcRbBlocksCxx" : "MpcRbBlocksAsm", seg ? "> " : "");
 	c->relax_kernel_name = kn;
-	if (trace_on()) { fprintf(stderr, "[mpcgpu] relax band: %s; lds=%zu B occ=%d grid=%u\n", c->tiles_desc.c_str(), smem, occ, grid); fflush(stderr); }
+	if (trace_on()) {
+		char ord[24] = "pairs";
+		if (rp.by_rows) snprintf(ord, sizeof(ord), "blocks of %u rows", rp.by_rows);
+		fprintf(stderr, "[mpcgpu] relax band: %s; lds=%zu B occ=%d grid=%u cell order=%s\n", c->tiles_desc.c_str(), smem, occ, grid, ord);
+		fflush(stderr);
+	}
 	TimedSpan ts;
 	if (span_begin(c, 3, &ts)) return 1;
 	relax_band_select(true, g.use_win, merge_cxx, diag, seg, rp, grid, smem, c->stream);
