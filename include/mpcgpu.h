@@ -83,7 +83,9 @@ int mpcgpu_set_seqs(mpcgpu_ctx *ctx, uint32_t n, const uint8_t *const *seqs, con
  *   profiles[i]           profile of sequence i of the last set_seqs/set_seqs_registry (Mega::m_Profiles
  *                         via GetProfileByLabel): len[i] positions x nfeat letters, position-major
  * Call after every set_seqs (which drops the previous profiles). Everything downstream of the
- * emissions (posterior, sparsify, EA, relax, joins) is unchanged. */
+ * emissions (posterior, sparsify, EA, relax, joins) is unchanged. Structure profiles chain too (fb_chain_mega_kernel, kernels_fbc.h:
+ * consecutive pairs with the same row sequence swept back to back), per rows-per-lane bin under MPCGPU_FB_CHAIN_MEGA: see
+ * mpcgpu_stage_a_info. */
 int mpcgpu_set_mega(mpcgpu_ctx *ctx, uint32_t nfeat, const uint32_t *alpha, const float *weight,
                     const float *const *logprobs, const float *const *logprob_mx,
                     const uint8_t *const *profiles);
@@ -109,7 +111,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_store_complete (the same values in records of every sequence), mpcgpu_values_info, mpcgpu_values_slice,
  *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
  *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
- *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
+ *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_chain_bins, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
  *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
  * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
@@ -374,8 +376,17 @@ int mpcgpu_timers_get(mpcgpu_ctx *ctx, float ms[MPCGPU_NKERNELS], uint64_t launc
 int mpcgpu_work_get(mpcgpu_ctx *ctx, uint64_t *dp_cells, uint64_t *relax_entry_z, uint64_t *store_entries);
 /* How the last stage A (mpcgpu_calc_posteriors / a pair-list call) ran its forward/backward sweeps: pairs in all, pairs that
  * ran as members of chains (consecutive pairs with the same row sequence swept back to back by one wavefront, no systolic
- * fill/drain in between: kernels_fbc.h), and the number of chains. Same cells, same results; MPCGPU_FB_CHAIN=0 turns chains off. */
+ * fill/drain in between: kernels_fbc.h), and the number of chains. Same cells, same results; MPCGPU_FB_CHAIN=0 turns chains off.
+ * With structure profiles loaded (mpcgpu_set_mega) the chains run in fb_chain_mega_kernel<H>, the chain kernel with the emissions of
+ * fb_kernel<H, true>, bin by bin (H rows per lane = rows of the row sequence / 64, rounded up) under MPCGPU_FB_CHAIN_MEGA: 0 = never
+ * (every pair alone in fb_kernel<H, true>), 1 = wherever the kernel launches, 2 = the rule: in bin H only where fb_chain_mega_kernel<H>
+ * is resident on a CU at least as often as fb_kernel<H, true> (the runtime's occupancy at the launch's workgroup size and LDS) and
+ * uses no scratch memory. Unset is 0 (the kernel is opt-in until its device time is on record). */
 int mpcgpu_stage_a_info(mpcgpu_ctx *ctx, uint64_t *pairs, uint64_t *chained_pairs, uint64_t *chains);
+/* bins: bit H set = the last stage A ran the pairs of bin H (H rows per lane) that can chain through the chain kernel (fb_chain_kernel,
+ * fb_chain_post_kernel or, with structure profiles, fb_chain_mega_kernel), chains of one pair included; 0 when every pair ran in fb_kernel
+ * or the row-block kernels. The bins of mpcgpu_stage_a_fuse_info are a subset. */
+int mpcgpu_stage_a_chain_bins(mpcgpu_ctx *ctx, uint32_t *bins);
 /* How the last stage A ran the pairs whose row sequence is cut into row blocks (769 residues or more: CalcFwdFlat, fwdflat3.cpp:12-153 /
  * CalcBwdFlat, bwdflat3.cpp:10-184 over blocks of 64 x 7 or 64 x 4 rows): pairs = the row-block pairs that ran cooperatively, the
  * wavefronts of a workgroup sweeping the blocks of ONE pair as a pipeline (kernels_fbcoop.h) where otherwise one wavefront walks them

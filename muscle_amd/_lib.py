@@ -19,7 +19,7 @@ SYMBOLS = [
     "mpcgpu_set_seqs", "mpcgpu_set_mega", "mpcgpu_pair_count", "mpcgpu_calc_posteriors", "mpcgpu_build_store",
     "mpcgpu_shard_info", "mpcgpu_shard_export", "mpcgpu_store_import", "mpcgpu_values_info", "mpcgpu_values_slice", "mpcgpu_values_export", "mpcgpu_values_import",
     "mpcgpu_cons_iter", "mpcgpu_cons_commit", "mpcgpu_cons_commit_range", "mpcgpu_get_ea", "mpcgpu_get_nnz", "mpcgpu_get_sparse",
-    "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_stage_a_coop_info", "mpcgpu_stage_a_fuse_info", "mpcgpu_post_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
+    "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_stage_a_chain_bins", "mpcgpu_stage_a_coop_info", "mpcgpu_stage_a_fuse_info", "mpcgpu_post_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
     "mpcgpu_work_get", "mpcgpu_synchronize", "mpcgpu_relax_info", "mpcgpu_shard_entries",
     "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch", "mpcgpu_store_epoch",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
@@ -98,6 +98,7 @@ def load(lib_path=None):
     L.mpcgpu_stage_a_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mpcgpu_stage_a_coop_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
     L.mpcgpu_stage_a_fuse_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
+    L.mpcgpu_stage_a_chain_bins.argtypes = [vp, C.POINTER(u32)]
     L.mpcgpu_post_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_synchronize.argtypes = [vp]
     L.mpcgpu_relax_info.argtypes = [vp, C.c_char_p, u32, C.POINTER(i32)]
@@ -554,6 +555,13 @@ class MpcGpu:
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._ck(self.L.mpcgpu_stage_a_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def stage_a_chain_bins(self):
+        """the rows-per-lane bins (H = rows of the row sequence / 64, rounded up) the last stage A ran through the chain kernel
+        (fb_chain_kernel; with structure profiles fb_chain_mega_kernel, under MPCGPU_FB_CHAIN_MEGA)"""
+        b = C.c_uint32(0)
+        self._ck(self.L.mpcgpu_stage_a_chain_bins(self.h, C.byref(b)))
+        return {H for H in range(32) if b.value >> H & 1}
 
     def stage_a_coop_info(self):
         """(row-block pairs of the last stage A that ran with the waves of a workgroup on one pair, waves per pair); (0, 0): none"""

@@ -21,6 +21,12 @@
 // at forward step V + t = Vtot-1 - s + T-1, uniform over the wave, so its loads stay coalesced rows.
 // Every cell is the same expression of the same neighbours as in fb_kernel: results are bit-identical (the GPU and emulator
 // suites run every all-pairs set through both kernels, MPCGPU_FB_CHAIN=0 selects fb_kernel alone).
+//
+// Structure-profile emissions, MEGA = true (fb_chain_mega_kernel; opt-in per bin, MPCGPU_FB_CHAIN_MEGA): as in fb_kernel<H, true> the
+// front of dynamic LDS holds the feature tables, a row of X is a packed profile word and an insert score (loaded once per chain), and
+// what travels with a column is Y's packed word and insert score, loaded by the lane that enters the column from the chain member the
+// column belongs to (column 0 of a member and the steps past the axis load nothing) and shifted from lane to lane. The match score is
+// mpc_mega_match over the same operands in the same order; boundary resets, M plane, totals and candidate lists do not know the difference.
 #pragma once
 #include "kernels_fb.h"
 #include "kernels_post.h"
@@ -59,21 +65,26 @@ struct FbChainPostParams { FbChainParams c; FbChainPost post; };
 #define MPC_DEVICE_FENCE() ((void)0) // the emulator: lanes meet at the wave rendezvous that follows
 #endif
 
-template <int H, bool POST>
+template <int H, bool POST, bool MEGA>
 __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbChainPost *pp)
 {
 	const FbParams &p = cp.f;
 	MPC_DYN_SMEM(smem_raw);
 	__shared__ MpcCoef s_coef[MPC_COEF_ENTRIES];
-	float *s_match = (float *)smem_raw; // A*A
-	float *s_ins = s_match + p.A * p.A; // A
-	u32 *s_tab_all = (u32 *)(s_ins + p.A); // per-wave chain tables
+	float *s_match = (float *)smem_raw; // A*A (MEGA: the feature tables, mg_tab_floats floats)
+	float *s_ins = s_match + p.A * p.A; // A   (MEGA: unused)
+	u32 *s_tab_all = MEGA ? (u32 *)(s_match + p.mg_tab_floats) : (u32 *)(s_ins + p.A); // per-wave chain tables
 	if (threadIdx.x < MPC_COEF_ENTRIES)
 		mpc_coef_table_init(s_coef, (int)threadIdx.x);
-	for (int q = threadIdx.x; q < p.A * p.A; q += blockDim.x)
-		s_match[q] = p.match[q];
-	for (int q = threadIdx.x; q < p.A; q += blockDim.x)
-		s_ins[q] = p.ins[q];
+	if (MEGA) {
+		for (u32 q = threadIdx.x; q < p.mg_tab_floats; q += blockDim.x)
+			s_match[q] = p.mg_tab[q];
+	} else {
+		for (int q = threadIdx.x; q < p.A * p.A; q += blockDim.x)
+			s_match[q] = p.match[q];
+		for (int q = threadIdx.x; q < p.A; q += blockDim.x)
+			s_ins[q] = p.ins[q];
+	}
 	__syncthreads();
 
 	const int t = threadIdx.x & 63;
@@ -87,6 +98,9 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 	const float tII = p.tII, tIM = p.tIM, tJJ = p.tJJ, tJM = p.tJM;
 	const int A = p.A;
 	const int NONE_HI = 0x7fffffff, NONE_LO = -0x40000000;
+	u32 mg_base[MPC_MEGA_FMAX], mg_alpha[MPC_MEGA_FMAX]; // wave-uniform (SGPRs), as in fb_kernel
+#pragma unroll
+	for (int f = 0; f < MPC_MEGA_FMAX; ++f) { mg_base[f] = MEGA ? p.mg_base[f] : 0u; mg_alpha[f] = MEGA ? p.mg_alpha[f] : 0u; }
 	// wave-uniform reads of the chain table
 	auto tabw = [&](int k, int w) -> u32 { return mpc_wave_first(s_tab[k * MPC_CHAIN_TAB_WORDS + w]); };
 
@@ -124,32 +138,48 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 		auto LYof = [&](int k) { return (int)tabw(k, 0); };
 		auto baseof = [&](int k) { return (int)tabw(k, 1); };
 		auto Yof = [&](int k) { return p.seq_code + p.seq_off[tabw(k, 3)]; };
+		// MEGA: packed letters and insert score of every position of X (fixed for the chain) and of a member's Y
+		const u64 *PX = MEGA ? p.mg_prof + p.seq_off[sx] : nullptr;
+		const float *IX = MEGA ? p.mg_ins + p.seq_off[sx] : nullptr;
+		auto PYof = [&](int k) { return p.mg_prof + p.seq_off[tabw(k, 3)]; };
+		auto IYof = [&](int k) { return p.mg_ins + p.seq_off[tabw(k, 3)]; };
 
 		// ------------------------------------------------------------------ forward
 		float cM[H], cIX[H], cJX[H], cIY[H], cJY[H]; // own rows at the previous column
 		float insx[H];
 		int mrow[H];
+		u64 xl[MEGA ? H : 1];
 #pragma unroll
 		for (int r = 0; r < H; ++r) {
 			const int i = t * H + r + 1;
-			const int xc = (i <= LX) ? (int)X[i - 1] : 0;
-			insx[r] = s_ins[xc];
-			mrow[r] = xc * A;
+			if (MEGA) {
+				xl[MEGA ? r : 0] = (i <= LX) ? PX[i - 1] : 0ull;
+				insx[r] = (i <= LX) ? IX[i - 1] : 0.0f; // fwdflat_mega.cpp:113
+			} else {
+				const int xc = (i <= LX) ? (int)X[i - 1] : 0;
+				insx[r] = s_ins[xc];
+				mrow[r] = xc * A;
+			}
 			cM[r] = cIX[r] = cJX[r] = cIY[r] = cJY[r] = LZ;
 		}
 		float uM = LZ, uIX = LZ, uJX = LZ, uIY = LZ, uJY = LZ; // row t*H at column V-1 (diagonal of r=0)
 		float gIY = LZ, gJY = LZ;                              // lane 0: row-0 chain (fwdflat3.cpp:81-93)
 		int yprev = 0;
+		u32 ylo_prev = 0, yhi_prev = 0; // MEGA: the column's packed letters and insert score travel with it
+		float insy_prev = 0.0f;
 		// lane 0's pair (it loads the letters), the boundary inside the wave, the pair whose last column lane T-1 reaches next
 		int k0 = 0, base0 = 0, LY0 = LYof(0), next0 = (C > 1) ? baseof(1) : NONE_HI;
-		const u8 *Y0 = Yof(0);
+		const u8 *Y0 = MEGA ? nullptr : Yof(0);
+		const u64 *PY0 = MEGA ? PYof(0) : nullptr;
+		const float *IY0 = MEGA ? IYof(0) : nullptr;
 		int kb = 1, vb = (C > 1) ? baseof(1) : NONE_HI; // first boundary not yet passed by lane T-1
 		int ke = 0, ve = LYof(0);                        // V of pair ke's last column
 		const int nsteps = Vtot + T - 1;
 		for (int s = 0; s < nsteps; ++s) {
 			const int V = s - t;
 			if (s == next0) { // lane 0 enters pair k0+1 at its column 0
-				++k0; base0 = next0; LY0 = LYof(k0); Y0 = Yof(k0);
+				++k0; base0 = next0; LY0 = LYof(k0);
+				if (MEGA) { PY0 = PYof(k0); IY0 = IYof(k0); } else Y0 = Yof(k0);
 				next0 = (k0 + 1 < C) ? baseof(k0 + 1) : NONE_HI;
 			}
 			const int j0 = s - base0; // lane 0's column within its pair
@@ -158,11 +188,28 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 			float nJX = mpc_lane_up1(cJX[H - 1]);
 			float nIY = mpc_lane_up1(cIY[H - 1]);
 			float nJY = mpc_lane_up1(cJY[H - 1]);
-			int yc = mpc_lane_up1(yprev);
-			const int yload = (j0 >= 1 && j0 <= LY0) ? (int)Y0[j0 - 1] : 0; // lane 0: letter of its column
-			if (t == 0)
-				yc = yload;
-			const float insy = s_ins[yc];
+			int yc = 0;
+			u32 ylo = 0, yhi = 0;
+			float insy;
+			u32 yi[MEGA ? MPC_MEGA_FMAX : 1];
+			if (MEGA) {
+				ylo = (u32)mpc_lane_up1((int)ylo_prev);
+				yhi = (u32)mpc_lane_up1((int)yhi_prev);
+				insy = mpc_lane_up1(insy_prev);
+				const bool incol = (j0 >= 1 && j0 <= LY0); // column 0 of a member and the steps past the axis load nothing
+				const u64 yload = incol ? PY0[j0 - 1] : 0ull;  // lane 0: its column's word, from the member the column belongs to
+				const float iload = incol ? IY0[j0 - 1] : 0.0f; // fwdflat_mega.cpp:120
+				if (t == 0) { ylo = (u32)yload; yhi = (u32)(yload >> 32); insy = iload; }
+#pragma unroll
+				for (int f = 0; f < MPC_MEGA_FMAX; ++f)
+					yi[f] = mg_base[f] + (((f < 4 ? ylo : yhi) >> (8 * (f & 3))) & 0xffu);
+			} else {
+				yc = mpc_lane_up1(yprev);
+				const int yload = (j0 >= 1 && j0 <= LY0) ? (int)Y0[j0 - 1] : 0; // lane 0: letter of its column
+				if (t == 0)
+					yc = yload;
+				insy = s_ins[yc];
+			}
 			if (t == 0) { // row 0: kernels_fb.h:243-251
 				nM = LZ; nIX = LZ; nJX = LZ;
 				if (j0 <= 0) { nIY = LZ; nJY = LZ; }
@@ -181,7 +228,8 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 #pragma unroll
 			for (int r = 0; r < H; ++r) {
 				const float oM = cM[r], oIX = cIX[r], oJX = cJX[r], oIY = cIY[r], oJY = cJY[r]; // (i, j-1)
-				const float m = s_match[mrow[r] + yc];
+				const float m = MEGA ? mpc_mega_match(s_match, mg_alpha, xl[MEGA ? r : 0], yi) // fwdflat_mega.cpp:121
+				                     : s_match[mrow[r] + yc];
 				// fwdflat3.cpp:116-145, as in fb_kernel
 				float vM = mpc_la5t(dM + tMM, dIX + tIM, dJX + tJM, dIY + tIM, dJY + tJM, s_coef) + m;
 				float vIX = mpc_la2t(upIX + tII, upM + tMI, s_coef) + insx[r];
@@ -199,6 +247,7 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 			}
 			uM = nM; uIX = nIX; uJX = nJX; uIY = nIY; uJY = nJY;
 			yprev = yc;
+			ylo_prev = ylo; yhi_prev = yhi; insy_prev = insy;
 			const int VT = s - (T - 1); // lane T-1's column
 			if (VT == ve) {
 				// F(LX, LY, *) of pair ke sits in lane T-1, row (LX-1)%H: totalprobflat.cpp:3-16 as in fb_kernel
@@ -236,16 +285,24 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 #pragma unroll
 		for (int r = 0; r < H; ++r) {
 			const int i = t * H + r + 1;
-			const int xc = (i < LX) ? (int)X[i] : 0;
-			insx[r] = s_ins[xc];
-			mrow[r] = xc * A;
+			if (MEGA) {
+				xl[MEGA ? r : 0] = (i < LX) ? PX[i] : 0ull;
+				insx[r] = (i < LX) ? IX[i] : 0.0f; // bwdflat_mega.cpp:55
+			} else {
+				const int xc = (i < LX) ? (int)X[i] : 0;
+				insx[r] = s_ins[xc];
+				mrow[r] = xc * A;
+			}
 			cM[r] = cIX[r] = cJX[r] = cIY[r] = cJY[r] = LZ; // virtual column LY+1 of the last pair
 		}
 		float gM = LZ; // row (t+1)*H+1 at column V+1: diagonal of r=H-1
 		int ynext_prev = 0;
+		ylo_prev = 0; yhi_prev = 0; insy_prev = 0.0f;
 		// the leading lane's pair (letters, the corner cell); the pairs above (A) and below (B) the boundary inside the wave
 		int kl = C - 1, basel = baseof(kl), LYl = LYof(kl);
-		const u8 *Yl = Yof(kl);
+		const u8 *Yl = MEGA ? nullptr : Yof(kl);
+		const u64 *PYl = MEGA ? PYof(kl) : nullptr;
+		const float *IYl = MEGA ? IYof(kl) : nullptr;
 		int ka = C - 1;
 		int baseA = baseof(ka), baseB = (ka >= 1) ? baseof(ka - 1) : 0;
 		int vbB = (ka >= 1) ? baseA : NONE_LO; // the boundary inside (or ahead of) the wave: column 0 of pair A
@@ -257,18 +314,36 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 			const int Vlead = Vtot - 1 - s; // lane T-1's column
 			const int V = Vlead + (T - 1 - t);
 			if (Vlead < basel && kl > 0) { // the leading lane moves into the pair below
-				--kl; basel = baseof(kl); LYl = LYof(kl); Yl = Yof(kl);
+				--kl; basel = baseof(kl); LYl = LYof(kl);
+				if (MEGA) { PYl = PYof(kl); IYl = IYof(kl); } else Yl = Yof(kl);
 			}
 			const int jl = Vlead - basel;
 			float nM = mpc_lane_down1(cM[0]);
 			float nIX = mpc_lane_down1(cIX[0]);
 			float nJX = mpc_lane_down1(cJX[0]);
 			if (t == 63) { nM = LZ; nIX = LZ; nJX = LZ; } // nothing below the wave: virtual row
-			int yc = mpc_lane_down1(ynext_prev);
-			const int yload = (jl >= 0 && jl < LYl) ? (int)Yl[jl] : 0; // y_{j+1} of the leading lane's column
-			if (t >= T - 1)
-				yc = yload; // leading lane (and idle lanes beyond it)
-			const float insy = s_ins[yc];
+			int yc = 0;
+			u32 ylo = 0, yhi = 0;
+			float insy;
+			u32 yi[MEGA ? MPC_MEGA_FMAX : 1];
+			if (MEGA) {
+				ylo = (u32)mpc_lane_down1((int)ylo_prev);
+				yhi = (u32)mpc_lane_down1((int)yhi_prev);
+				insy = mpc_lane_down1(insy_prev);
+				const bool ycol = (jl >= 0 && jl < LYl);
+				const u64 yload = ycol ? PYl[jl] : 0ull;    // y_{j+1} of the leading lane's column, from the member it is in
+				const float iload = ycol ? IYl[jl] : 0.0f; // bwdflat_mega.cpp:78
+				if (t >= T - 1) { ylo = (u32)yload; yhi = (u32)(yload >> 32); insy = iload; }
+#pragma unroll
+				for (int f = 0; f < MPC_MEGA_FMAX; ++f)
+					yi[f] = mg_base[f] + (((f < 4 ? ylo : yhi) >> (8 * (f & 3))) & 0xffu);
+			} else {
+				yc = mpc_lane_down1(ynext_prev);
+				const int yload = (jl >= 0 && jl < LYl) ? (int)Yl[jl] : 0; // y_{j+1} of the leading lane's column
+				if (t >= T - 1)
+					yc = yload; // leading lane (and idle lanes beyond it)
+				insy = s_ins[yc];
+			}
 			const bool corner = jl == LYl; // lane T-1 stands on (., LY) of its pair: bwdflat3.cpp:53-61 for row LX
 			const int sf = Vlead + T - 1;  // forward step that stored this lane's column V (= V + t)
 			const float *fmrow = fm + ((u64)(sf < 0 ? 0 : sf) * H) * 64 + t;
@@ -285,7 +360,8 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 				const int i = t * H + r + 1;
 				const float oM = cM[r], oIY = cIY[r], oJY = cJY[r]; // (i, j+1)
 				// bwdflat3.cpp:75-79
-				const float xM = dgM + s_match[mrow[r] + yc];
+				const float xM = dgM + (MEGA ? mpc_mega_match(s_match, mg_alpha, xl[MEGA ? r : 0], yi) // bwdflat_mega.cpp:79-80
+				                             : s_match[mrow[r] + yc]);
 				const float xIX = dnIX + insx[r];
 				const float xJX = dnJX + insx[r];
 				const float xIY = oIY + insy;
@@ -310,6 +386,7 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 			}
 			gM = nM;
 			ynext_prev = yc;
+			ylo_prev = ylo; yhi_prev = yhi; insy_prev = insy;
 			if (V == vbB) { // this was column 0 of pair A; for pair B it stands where the virtual column LY+1 is
 #pragma unroll
 				for (int r = 0; r < H; ++r) cM[r] = cIX[r] = cJX[r] = cIY[r] = cJY[r] = LZ;
@@ -393,7 +470,15 @@ __device__ __forceinline__ void fb_chain_body(const FbChainParams &cp, const FbC
 template <int H>
 __global__ void __launch_bounds__(256, (H == 8) ? 4 : 1) fb_chain_kernel(FbChainParams cp)
 {
-	fb_chain_body<H, false>(cp, nullptr);
+	fb_chain_body<H, false, false>(cp, nullptr);
+}
+
+// the chains of structure-profile input (MEGA = true: emissions as in fb_kernel<H, true>). An entry point of its own name: the byte
+// kernel's symbol is what the listing checks and the issue-cost census look up. Registers: no bound beyond the workgroup's, as fb_kernel<H, true>.
+template <int H>
+__global__ void __launch_bounds__(256, 1) fb_chain_mega_kernel(FbChainParams cp)
+{
+	fb_chain_body<H, false, true>(cp, nullptr);
 }
 
 // the same sweeps, and every chain's pairs finished by the wave that swept them (see FbChainPost). Up to 8 rows per lane the sweeps fit 128
@@ -401,5 +486,5 @@ __global__ void __launch_bounds__(256, (H == 8) ? 4 : 1) fb_chain_kernel(FbChain
 template <int H>
 __global__ void __launch_bounds__(256, (H <= 8) ? 4 : 1) fb_chain_post_kernel(FbChainPostParams cp)
 {
-	fb_chain_body<H, true>(cp.c, &cp.post);
+	fb_chain_body<H, true, false>(cp.c, &cp.post);
 }

@@ -258,6 +258,7 @@ struct mpcgpu_ctx {
 	DevBuf d_rest, d_rest_n, d_res_n, d_nnz_n, d_ea_n, d_flags_n, d_fuse_sort;
 	u64 sa_fused = 0; // last stage A: pairs finished inside the sweeps
 	u32 sa_fuse_bins = 0; // ... and the rows-per-lane bins they ran in (bit H)
+	u32 sa_chain_bins = 0; // last stage A: the bins that went through the chain kernel (bit H)
 	hipStream_t stream2 = nullptr;
 	hipEvent_t ev_post = nullptr;
 	u64 sa_pairs = 0, sa_chained = 0, sa_chains = 0; // last stage A: pairs, pairs that ran in chains, chains
@@ -488,38 +489,83 @@ void launch_fb_h(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_
 	}
 }
 
-// fb_chain_kernel (kernels_fbc.h): chains of pairs that share their row sequence
-template <int H> void launch_fbc(const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+// fb_chain_kernel / fb_chain_mega_kernel (kernels_fbc.h): chains of pairs that share their row sequence; MEGA: structure-profile emissions
+template <int H, bool MEGA> void launch_fbc(const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-	auto kern = fb_chain_kernel<H>;
-	ensure_dyn_smem((const void *)kern, smem);
-	MPC_LAUNCH(kern, grid, block, smem, st, p);
-}
-
-template <int H> int occ_fbc(u32 block, size_t smem)
-{
-	int nb = 0;
-	ensure_dyn_smem((const void *)fb_chain_kernel<H>, smem);
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fb_chain_kernel<H>, (int)block, smem) != hipSuccess || nb < 1)
-		nb = 1;
-	return nb;
-}
-
-int occ_fbc_h(int H, u32 block, size_t smem)
-{
-	switch (H) {
-#define MPC_CASE(h) case h: return occ_fbc<h>(block, smem);
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: return 1;
+	if (MEGA) {
+		auto kern = fb_chain_mega_kernel<H>;
+		ensure_dyn_smem((const void *)kern, smem);
+		MPC_LAUNCH(kern, grid, block, smem, st, p);
+	} else {
+		auto kern = fb_chain_kernel<H>;
+		ensure_dyn_smem((const void *)kern, smem);
+		MPC_LAUNCH(kern, grid, block, smem, st, p);
 	}
 }
 
-void launch_fbc_h(int H, const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+// workgroups a CU keeps resident, as the runtime reports them (0: such a workgroup does not fit, or no answer)
+template <int H, bool MEGA> int occ_fbc_raw(u32 block, size_t smem)
+{
+	int nb = 0;
+	const void *fn = MEGA ? (const void *)fb_chain_mega_kernel<H> : (const void *)fb_chain_kernel<H>;
+	ensure_dyn_smem(fn, smem);
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)block, smem) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
+	return nb < 0 ? 0 : nb;
+}
+
+// ... for sizing grids and planes: at least 1
+int occ_fbc_h(int H, bool mega, u32 block, size_t smem)
+{
+	int nb = 0;
+	switch (H) {
+#define MPC_CASE(h) case h: nb = mega ? occ_fbc_raw<h, true>(block, smem) : occ_fbc_raw<h, false>(block, smem); break;
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: break;
+	}
+	return nb < 1 ? 1 : nb;
+}
+
+// ... of fb_chain_mega_kernel<H>, unclamped: chain_plan compares it with fb_kernel<H, true>'s and drops a bin whose workgroup does not fit
+int occ_fbcm_fit_h(int H, u32 block, size_t smem)
 {
 	switch (H) {
-#define MPC_CASE(h) case h: launch_fbc<h>(p, grid, block, smem, st); break;
+#define MPC_CASE(h) case h: return occ_fbc_raw<h, true>(block, smem);
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: return 0;
+	}
+}
+
+// does fb_chain_mega_kernel<H> keep values in scratch memory (the register allocator spilled)? The emulator has no registers to run out of.
+template <int H> bool fbcm_spills()
+{
+#ifdef MPC_EMU
+	return false;
+#else
+	hipFuncAttributes a;
+	if (hipFuncGetAttributes(&a, (const void *)fb_chain_mega_kernel<H>) != hipSuccess) { (void)hipGetLastError(); return true; }
+	return a.localSizeBytes != 0;
+#endif
+}
+
+bool fbcm_spills_h(int H)
+{
+	switch (H) {
+#define MPC_CASE(h) case h: return fbcm_spills<h>();
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: return true;
+	}
+}
+
+void launch_fbc_h(int H, bool mega, const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+{
+	switch (H) {
+#define MPC_CASE(h) case h: if (mega) launch_fbc<h, true>(p, grid, block, smem, st); else launch_fbc<h, false>(p, grid, block, smem, st); break;
 	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
 	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
 #undef MPC_CASE
@@ -1143,6 +1189,13 @@ int mpcgpu_stage_a_info(mpcgpu_ctx *c, uint64_t *pairs, uint64_t *chained_pairs,
 	if (pairs) *pairs = c->sa_pairs;
 	if (chained_pairs) *chained_pairs = c->sa_chained;
 	if (chains) *chains = c->sa_chains;
+	return 0;
+}
+
+int mpcgpu_stage_a_chain_bins(mpcgpu_ctx *c, uint32_t *bins)
+{
+	if (!c) return 1;
+	if (bins) *bins = c->sa_chain_bins;
 	return 0;
 }
 

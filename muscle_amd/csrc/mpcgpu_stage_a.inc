@@ -86,7 +86,9 @@ struct BatchPrep {
 // Chains: consecutive pairs of the list with the same row sequence (the all-pairs order is full of them), each with
 // LY + 1 >= T (kernels_fbc.h), up to MPCGPU_FB_CHAIN_MAX (default 16) pairs and as many columns as the forward M planes of the
 // resident waves may take (a quarter of the free memory, 32 GB at most). MPCGPU_FB_CHAIN=0: every pair on its own (fb_kernel).
+// With structure profiles (g.mega) the chains run in fb_chain_mega_kernel, bin by bin under MPCGPU_FB_CHAIN_MEGA (chain_plan).
 struct ChainPlan {
+	bool mega = false; // the chain kernel's MEGA instantiations (smem: the feature tables in front of the chain tables)
 	bool on = false, grade = true; // grade = false: no shorter chains at the end of a launch (MPCGPU_FB_CHAIN_GRADE=0: tests)
 	u32 max = 0; size_t smem = 0;
 	u32 vcap[MPC_HMAX + 1] = {0}; // columns a chain of a rows-per-lane bin may have; 0: the bin takes no chains
@@ -114,7 +116,7 @@ static int fuse_plan(mpcgpu_ctx *c, const StageAGeom &g, u64 np, u64 batch_budge
 {
 	const int env = env_int("MPCGPU_FB_POST_FUSE", kFbPostFuseDefault);
 	cp.post_batch = (u32)std::min(std::max(env_int("MPCGPU_POST_BATCH", 64), 1), 64);
-	if (!cp.on || !post_rows || env == 0) return 0;
+	if (!cp.on || cp.mega || !post_rows || env == 0) return 0; // (the fused kernel is byte-only)
 	size_t freeb = 0, totb = 0;
 	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
 	const u64 owned = (u64)c->d_cand.cap + c->d_res.cap + c->d_res_n.cap + c->d_fm.cap;
@@ -126,7 +128,7 @@ static int fuse_plan(mpcgpu_ctx *c, const StageAGeom &g, u64 np, u64 batch_budge
 	const u32 top = std::max(std::min<u32>(g.capc, sort_cap), 2u);
 	for (u32 H = 1; H <= MPC_HMAX; ++H) {
 		if (!cp.vcap[H]) continue;
-		const int occ0 = occ_fbc_h((int)H, SA_BLOCK, cp.smem);
+		const int occ0 = occ_fbc_h((int)H, false, SA_BLOCK, cp.smem);
 		if (env != 1 && fbcp_spills_h((int)H)) continue; // held to the sweeps' registers, the finishing code spilled: not by the rule
 		const int occ2 = occ_fbcp_h((int)H, SA_BLOCK, fuse_smem(cp, g, 2));
 		const int need = occ2 >= occ0 ? occ0 : env == 1 ? 1 : occ0;
@@ -140,23 +142,42 @@ static int fuse_plan(mpcgpu_ctx *c, const StageAGeom &g, u64 np, u64 batch_budge
 	}
 	return 0;
 }
+// MPCGPU_FB_CHAIN_MEGA. Which bins chain when structure profiles are loaded (fb_chain_mega_kernel<H> in place of fb_kernel<H, true>). 0: none.
+// 1: every bin whose workgroup the chip takes. 2 (the rule): bin H only where fb_chain_mega_kernel<H> is resident at least as often as
+// fb_kernel<H, true> — workgroups per CU at SA_BLOCK threads, each with its own LDS — and uses no scratch memory: the chain kernel
+// carries the chain's bookkeeping beside the sweep's registers, and a bin that paid for it with residency would lose more than the fill
+// and drain it saves. Unset is 0: the rule becomes the default only when every bin it enables has been MEASURED no slower than
+// fb_kernel<H, true> beyond the run-to-run spread (DESIGN.md 4.1).
+static const int kFbChainMegaDefault = 0;
 static int chain_plan(mpcgpu_ctx *c, const StageAGeom &g, u64 planes_budget, ChainPlan &cp)
 {
-	cp.on = !g.mega && env_int("MPCGPU_FB_CHAIN", 1) != 0;
+	const int mega_env = g.mega ? env_int("MPCGPU_FB_CHAIN_MEGA", kFbChainMegaDefault) : 1;
+	cp.mega = g.mega;
+	cp.on = env_int("MPCGPU_FB_CHAIN", 1) != 0 && mega_env != 0;
 	cp.max = (u32)std::min(std::max(env_int("MPCGPU_FB_CHAIN_MAX", 16), 2), MPC_CHAIN_MAX);
 	cp.grade = env_int("MPCGPU_FB_CHAIN_GRADE", 1) != 0;
-	cp.smem = ((size_t)c->A * c->A + c->A) * sizeof(float) + (size_t)SA_WAVES * MPC_CHAIN_TAB_BYTES;
+	cp.smem = g.fb_smem + (size_t)SA_WAVES * MPC_CHAIN_TAB_BYTES; // the emission tables (MEGA: the feature tables), then the waves' chain tables
 	if (!cp.on) return 0;
 	size_t freeb = 0, totb = 0;
 	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
 	// (a quarter of what is free, 32 GB at most — and no more than MPCGPU_SCRATCH_GB where that is set: several contexts on one
 	// device, e.g. the eight of tests/test_gpu_parity.py::test_group_of_eight_contexts_config3_digests, each see the same free memory)
 	const u64 fm_budget = std::min<u64>(std::min<u64>((u64)32 << 30, planes_budget), (u64)((freeb + c->d_fm.cap) * 0.25));
+	bool any = false;
 	for (u32 H = 1; H <= MPC_HMAX; ++H) {
-		const u64 waves = (u64)c->prop.multiProcessorCount * (u32)occ_fbc_h((int)H, SA_BLOCK, cp.smem) * SA_WAVES;
+		if (g.mega) { // the bin chains only where the knob lets it; elsewhere vcap stays 0 and build_chains leaves its pairs to fb_kernel
+			const int occ_c = occ_fbcm_fit_h((int)H, SA_BLOCK, cp.smem);
+			bool take = occ_c >= 1;
+			if (take && mega_env != 1) take = occ_c >= occ_fb_h((int)H, true, SA_BLOCK, g.fb_smem) && !fbcm_spills_h((int)H);
+			if (trace_on()) { fprintf(stderr, "[mpcgpu] fb chain mega: H=%u %s (workgroups per CU: chain %d, single %d)\n", H, take ? "chains" : "stays on fb_kernel", occ_c, occ_fb_h((int)H, true, SA_BLOCK, g.fb_smem)); fflush(stderr); }
+			if (!take) continue;
+		}
+		const u64 waves = (u64)c->prop.multiProcessorCount * (u32)occ_fbc_h((int)H, g.mega, SA_BLOCK, cp.smem) * SA_WAVES;
 		const u64 steps = fm_budget / (waves * H * 64 * 4);
 		cp.vcap[H] = steps > 64 + 2 ? (u32)std::min<u64>(steps - 64, 1u << 24) : 0;
+		any = any || cp.vcap[H];
 	}
+	if (g.mega && !any) cp.on = false; // no bin chains: the stage is the one MPCGPU_FB_CHAIN_MEGA=0 runs
 	return 0;
 }
 
@@ -202,7 +223,7 @@ static void build_chains(const mpcgpu_ctx *c, const ChainPlan &cp, u32 long_min,
 		size_t hi = lo;
 		while (hi < chains.size() && chains[hi].H == chains[lo].H) ++hi;
 		const u32 H = chains[lo].H;
-		const u64 waves = (u64)c->prop.multiProcessorCount * (u32)occ_fbc_h((int)H, SA_BLOCK, cp.smem) * SA_WAVES;
+		const u64 waves = (u64)c->prop.multiProcessorCount * (u32)occ_fbc_h((int)H, cp.mega, SA_BLOCK, cp.smem) * SA_WAVES;
 		const u64 gw = std::max<u64>(waves, 1); // pairs per grade: one round of the resident waves
 		u64 seen = 0; // pairs, counted from the end of the bin
 		for (size_t k = hi; k-- > lo;) {
@@ -478,7 +499,7 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 		const u32 cnt = P.ccount[H];
 		const bool fuse = plan.fuse[H];
 		const size_t smem = fuse ? fuse_smem(plan, g, plan.fuse_sort_cap[H]) : plan.smem;
-		const u32 occ = (u32)std::max(fuse ? occ_fbcp_h((int)H, SA_BLOCK, smem) : occ_fbc_h((int)H, SA_BLOCK, plan.smem), 1);
+		const u32 occ = (u32)std::max(fuse ? occ_fbcp_h((int)H, SA_BLOCK, smem) : occ_fbc_h((int)H, plan.mega, SA_BLOCK, plan.smem), 1);
 		const u32 grid = std::max(std::min<u32>((cnt + SA_WAVES - 1) / SA_WAVES, cus * occ), 1u);
 		const u64 fm_stride = (u64)(P.cvmax[H] + 64) * H * 64;
 		HIPCHK(c, c->d_fm.ensure((u64)grid * SA_WAVES * fm_stride * 4));
@@ -509,7 +530,7 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 			launch_fbcp_h((int)H, fpp, grid, SA_BLOCK, smem, c->stream);
 		} else {
 			if (span_begin(c, 0, &sp)) return 1;
-			launch_fbc_h((int)H, cp, grid, SA_BLOCK, plan.smem, c->stream);
+			launch_fbc_h((int)H, plan.mega, cp, grid, SA_BLOCK, plan.smem, c->stream);
 		}
 		HIPCHK(c, hipGetLastError());
 		if (span_end(c, &sp)) return 1;
@@ -767,7 +788,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 	c->sh_ea.assign(np, 0.0f);
 	StageAGeom g = stage_a_geom(c, np, px, py);
 	c->work_cells = g.work_cells;
-	c->sa_pairs = np; c->sa_chained = c->sa_chains = 0;
+	c->sa_pairs = np; c->sa_chained = c->sa_chains = 0; c->sa_chain_bins = 0;
 	c->sa_coop_pairs = 0; c->sa_coop_waves = 0;
 	const u64 hdr = shard_header_bytes(np);
 	if (np == 0) {
@@ -856,6 +877,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 		for (u32 c2 : cur.chain_cnt) if (c2 >= 2) { c->sa_chains += 1; c->sa_chained += c2; }
 		c->sa_fused += cur.fused;
 		for (u32 H = 1; H <= MPC_HMAX; ++H) if (chain.fuse[H] && cur.ccount[H]) c->sa_fuse_bins |= 1u << H;
+		for (u32 H = 1; H <= MPC_HMAX; ++H) if (cur.ccount[H]) c->sa_chain_bins |= 1u << H;
 		if (cur.coop_pairs) { c->sa_coop_pairs += cur.coop_pairs; c->sa_coop_waves = cur.coop_waves; }
 		std::swap(cur, nxt);
 		if (cur.valid) { // the next batch's index arrays become the current set
