@@ -15,7 +15,7 @@
 #                      - calcposteriorflat.o's CalcPosterior symbol, weakened with objcopy so that
 #                        hostcxx/mpcflat_gpu.cpp's strong definition wins while CalcPostFlat and the
 #                        two vestigial virtuals in the same object stay available; likewise one member each of
-#                        super7.o, uclust.o, pprog2.o and mpcflat.o (MPCFlat::CalcPosteriors) - see below
+#                        super7.o, uclust.o, pprog2.o, mpcflat.o (MPCFlat::CalcPosteriors) and swdistmx.o (CalcGuideTree_SW_BLOSUM62) - see below
 #   + hostcxx/mpcflat_gpu.cpp (g++, against the reference headers) + hostcxx/rand_isolate.cpp
 #     (-Wl,--wrap=rand) + -lmpcgpu
 set -euo pipefail
@@ -62,7 +62,14 @@ objcopy --weaken-symbol=_ZN7MPCFlat14CalcPosteriorsEv "$REFOBJ/mpcflat.o" "$OUT/
 # MPCFlat::ProgressiveAlign: ours (the joins of a guide-tree level in one library call); the reference's stays in the binary as
 # MPCFlat_ProgressiveAlign_ref (our fallback calls it); ProgAln, FreeProgMSAs, FreeSparsePosts of progalnflat.o stay as they are
 objcopy --redefine-sym _ZN7MPCFlat16ProgressiveAlignEv=MPCFlat_ProgressiveAlign_ref "$REFOBJ/progalnflat.o" "$OUT/progalnflat_weak.o"
-OBJS=$(ls "$REFOBJ"/*.o | grep -v -e '/super7\.o$' -e '/uclust\.o$' -e '/alignpairflat\.o$' -e '/pprog2\.o$' -e '/mpcflat\.o$' -e '/progalnflat\.o$' | grep -v -e '/consflat\.o$' -e '/alnalnsflat\.o$' -e '/alnmsasflat\.o$' -e '/calcposteriorflat\.o$' -e '/buildpostflat\.o$' -e '/refineflat\.o$')
+# CalcGuideTree_SW_BLOSUM62: ours (all-pairs Smith-Waterman scores from the device: the guide tree of -super7 / -super7_mega / -swdistmx
+# without a tree option). The symbol is weakened in swdistmx.o, so cmd_swdistmx in the same object reaches our definition like
+# cmd_super7 and cmd_super7_mega do; the reference's function stays reachable under a second, global name at the same address,
+# CalcGuideTree_SW_BLOSUM62_ref (MUSCLE_GPU_SW_TREE=0 calls it).
+SWSYM=_Z25CalcGuideTree_SW_BLOSUM62RK13MultiSequenceR4Tree
+read -r SWVAL SWSEC < <(objdump -t "$REFOBJ/swdistmx.o" | awk -v s="$SWSYM" '$NF == s && $2 == "g" { print $1, $4 }')
+objcopy --weaken-symbol="$SWSYM" --add-symbol "CalcGuideTree_SW_BLOSUM62_ref=$SWSEC:0x$SWVAL,global,function" "$REFOBJ/swdistmx.o" "$OUT/swdistmx_weak.o"
+OBJS=$(ls "$REFOBJ"/*.o | grep -v -e '/super7\.o$' -e '/uclust\.o$' -e '/alignpairflat\.o$' -e '/pprog2\.o$' -e '/mpcflat\.o$' -e '/progalnflat\.o$' -e '/swdistmx\.o$' | grep -v -e '/consflat\.o$' -e '/alnalnsflat\.o$' -e '/alnmsasflat\.o$' -e '/calcposteriorflat\.o$' -e '/buildpostflat\.o$' -e '/refineflat\.o$')
 # The product links libmpcgpu.so. tests/test_dropin_emu.py re-runs this script with
 # MPCGPU_LIBDIR/MPCGPU_LIBNAME pointing at the SIMT-emulator build of the same library sources
 # (tests/emu, test infrastructure) to check the host-side plumbing of this file without a GPU.
@@ -71,7 +78,7 @@ LIBNAME="${MPCGPU_LIBNAME:-mpcgpu}"
 BIN="${MPCGPU_BIN:-muscle_gpu}"
 # --wrap=rand: the reference's rand() (refineflat.cpp:14) gets a private copy of glibc's default
 # stream; the HIP runtime in the same process otherwise consumes it (hostcxx/rand_isolate.cpp)
-g++ -O3 -fopenmp -pthread -Wl,--wrap=rand $OBJS "$OUT/calcposteriorflat_weak.o" "$OUT/super7_weak.o" "$OUT/uclust_weak.o" "$OUT/pprog2_weak.o" "$OUT/mpcflat_weak.o" "$OUT/progalnflat_weak.o" "$OUT/mpcflat_gpu.o" "$OUT/rand_isolate.o" \
+g++ -O3 -fopenmp -pthread -Wl,--wrap=rand $OBJS "$OUT/calcposteriorflat_weak.o" "$OUT/super7_weak.o" "$OUT/uclust_weak.o" "$OUT/pprog2_weak.o" "$OUT/mpcflat_weak.o" "$OUT/progalnflat_weak.o" "$OUT/swdistmx_weak.o" "$OUT/mpcflat_gpu.o" "$OUT/rand_isolate.o" \
   -L"$LIBDIR" -l"$LIBNAME" -Wl,-rpath,'$ORIGIN/../../muscle_amd/csrc' -Wl,-rpath,"$LIBDIR" -Wl,-rpath,/opt/rocm/lib -o "$OUT/$BIN"
 echo "built: $OUT/$BIN"
 # the product binary, beside the compiled reference (same depth below the root: the $ORIGIN run path holds from there too)

@@ -40,6 +40,7 @@
 #include "mpcflat_mega.h"
 #include "super7.h"
 #include "uclust.h"
+#include "upgma5.h"
 #include "mpcgpu.h"
 
 #include <malloc.h>
@@ -372,10 +373,12 @@ bool DebugOn()
 
 // MUSCLE_GPU_TIMING=1: wall time spent inside the replaced functions, printed at exit (where does an
 // end-to-end run spend its time once the stage itself takes a few seconds).
-enum { T_STAGE_A, T_CONS_ITER, T_ALN_PREP, T_ALN_LIB, T_ALN_POST, T_JOIN_PREP, T_JOIN_LIB, T_PAIRS_PREP, T_PAIRS_LIB, T_COUNT };
+enum { T_STAGE_A, T_CONS_ITER, T_ALN_PREP, T_ALN_LIB, T_ALN_POST, T_JOIN_PREP, T_JOIN_LIB, T_PAIRS_PREP, T_PAIRS_LIB, T_SW_TREE, T_COUNT };
 // (atomics: the shrub and join workers of -super7 stop their watches concurrently — round-5 advisor finding)
 std::atomic<unsigned long long> g_Nanos[T_COUNT];
 std::atomic<unsigned long long> g_Calls[T_COUNT];
+std::atomic<unsigned long long> g_SwKernelNanos; // device time of sw_kernel inside the "guide tree (SW)" row (mpcgpu_sw_info)
+std::atomic<unsigned long long> g_SwCells;
 // The timeline of ONE MPCFlat::Run (muscle -align): when the replaced functions were entered first / left last, in ns since process
 // start. What lies BETWEEN them is the reference's own host code — the row f4 of SURVEY.md 8 (CalcGuideTree = UPGMA5,
 // upgma5.cpp:87-..., ClustalWeights, CalcJoinOrder, the bookkeeping of ProgAln / RefineIter, SortMSA, output) — which this file does
@@ -408,12 +411,15 @@ bool TimingOn()
 				{
 				static const char *Names[T_COUNT] = { "stage A (all pairs)", "ConsIter", "AlignAlns: maps",
 				  "AlignAlns: library", "AlignAlns: result MSA", "AlignMSAsFlat: pairs+maps", "AlignMSAsFlat: library",
-				  "AlignPairFlat lists: registry", "AlignPairFlat lists: library" };
+				  "AlignPairFlat lists: registry", "AlignPairFlat lists: library", "guide tree (SW)" };
 				fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  (static initialisation to exit handlers; the rows below are parts of it)\n",
 				  "process", std::chrono::duration<double>(std::chrono::steady_clock::now() - g_ProcessStart).count());
 				fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  (inside the first call below that needed it)\n", "context creation, HIP init", g_CtxSeconds);
 				for (int i = 0; i < T_COUNT; ++i)
 					fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  %8llu calls\n", Names[i], g_Nanos[i].load()*1e-9, g_Calls[i].load());
+				if (g_Calls[T_SW_TREE].load() != 0)
+					fprintf(stderr, "[muscle_gpu]   guide tree (SW): kernel %.3f s for %llu DP cells; the rest of the row is the letters' upload, the distance matrix and UPGMA5\n",
+					  g_SwKernelNanos.load()*1e-9, g_SwCells.load());
 				fprintf(stderr, "[muscle_gpu] posterior stage: computed %llu reused %llu\n", g_StagesComputed.load(), g_StagesReused.load());
 // (one MPCFlat::Run only: with the shrub workers of -super7 running many at once first-entered / last-left marks interleave)
 				const bool OneRun = g_Mark[M_POST_ENTER].load() != 0 && g_Mark[M_POST_ENTER].load() <= g_Mark[M_POST_EXIT].load() &&
@@ -1961,4 +1967,75 @@ void Super7::IntraAlignShrubs()
 	if (TimingOn())
 		fprintf(stderr, "[muscle_gpu] %u shrubs on %u worker contexts: entered %.3f s after process start, took %.3f s\n", ShrubCount, Workers,
 		  ShrubsBegin, std::chrono::duration<double>(std::chrono::steady_clock::now() - g_ProcessStart).count() - ShrubsBegin);
+	}
+
+// ---------------------------------------------------------------------------------------------------------------
+// CalcGuideTree_SW_BLOSUM62 (swdistmx.cpp:87-127): the guide tree `muscle -super7 in.fa` (super7.cpp:163-168), `-super7_mega` and
+// `-swdistmx` build when no tree or distance matrix is given. The reference runs SWFast_Seqs_BLOSUM62 (sw.cpp:287-295) per pair on
+// host threads; here the raw scores of all pairs come from mpcgpu_sw_scores on a context of the selected device, and everything
+// behind them is the reference's own: NormScore = Score / ((Li + Lj) / 2.0f) (swdistmx.cpp:75-76), the symmetric matrix, and
+// UPGMA5::Init / ScaleDistMx / Run(LINKAGE_Avg) (swdistmx.cpp:115-126).
+// Two things the reference does are left out. Its per-pair log line with the alignment path (swdistmx.cpp:81-82): no path exists,
+// the kernel computes no trace-back. And its death in that trace-back: TraceBackBitSW asserts Besti < LA (sw.cpp:73) with
+// Besti + 1 passed in, so the reference aborts whenever a pair's best local alignment ends on the last residue of either sequence;
+// the scores are complete before that point, and the tree built here is the tree those scores define.
+// MUSCLE_GPU_SW_TREE=0: the reference's own loop, kept in the binary as CalcGuideTree_SW_BLOSUM62_ref (hostcxx/build_muscle_gpu.sh).
+extern float Blosum62_sij[20][20]; // blosum.cpp:8
+extern "C" void CalcGuideTree_SW_BLOSUM62_ref(const MultiSequence &Input, Tree &T);
+void CalcGuideTree_SW_BLOSUM62(const MultiSequence &Input, Tree &T)
+	{
+	const char *Env = getenv("MUSCLE_GPU_SW_TREE");
+	const uint SeqCount = Input.GetSeqCount();
+	if ((Env != 0 && *Env == '0') || SeqCount < 2)
+		{
+		CalcGuideTree_SW_BLOSUM62_ref(Input, T);
+		return;
+		}
+	Stopwatch SW(T_SW_TREE);
+	vector<string> Labels;
+	vector<const uint8_t *> Ptrs;
+	vector<uint32_t> Lens;
+	for (uint i = 0; i < SeqCount; ++i)
+		{
+		Labels.push_back(Input.GetLabelStr(i));
+		const Sequence &Seq = *Input.GetSequence(i);
+		Ptrs.push_back(Seq.GetBytePtr());
+		Lens.push_back(Seq.GetLength());
+		}
+	const uint64_t PairCount = uint64_t(SeqCount)*(SeqCount - 1)/2;
+	vector<float> Scores(PairCount);
+		{
+// a context of its own, gone before the shrubs start: the scores need nothing of the posterior stage's state. mpcgpu_set_seqs_registry
+// wants pair-HMM tables first; none of them enters a score (InitProbcons has not run yet, super7.cpp:170).
+		mpcgpu_ctx *Ctx = 0;
+		if (mpcgpu_create(&Ctx, DeviceList()[0]) != 0)
+			Die("GPU guide tree: %s", mpcgpu_last_error(0));
+		GPUCHK(mpcgpu_set_hmm(Ctx, PairHMM::m_StartScore, &PairHMM::m_TransScore[0][0], &PairHMM::m_MatchScore[0][0],
+		  PairHMM::m_InsScore, MIN_SPARSE_SCORE, -1));
+		GPUCHK(mpcgpu_set_seqs_registry(Ctx, SeqCount, Ptrs.data(), Lens.data()));
+		GPUCHK(mpcgpu_sw_set_scores(Ctx, g_CharToLetterAmino, 20, &Blosum62_sij[0][0], -11, -1)); // swdistmx.cpp:106-107
+		GPUCHK(mpcgpu_sw_scores(Ctx, PairCount, 0, 0, Scores.data()));
+		uint64_t Info[6];
+		GPUCHK(mpcgpu_sw_info(Ctx, Info));
+		g_SwKernelNanos += Info[5];
+		g_SwCells += Info[1];
+		mpcgpu_destroy(Ctx);
+		}
+	vector<vector<float> > DistMxv(SeqCount);
+	for (uint i = 0; i < SeqCount; ++i)
+		DistMxv[i].assign(SeqCount, FLT_MAX); // the diagonal as DistMx.PutAll leaves it (swdistmx.cpp:99)
+	uint64_t k = 0;
+	for (uint i = 0; i < SeqCount; ++i)
+		for (uint j = i + 1; j < SeqCount; ++j)
+			{
+			float SWScore = Scores[k++];
+			float MeanLength = (Lens[i] + Lens[j])/2.0f;
+			float NormScore = SWScore/MeanLength;
+			DistMxv[i][j] = NormScore;
+			DistMxv[j][i] = NormScore;
+			}
+	UPGMA5 U;
+	U.Init(Labels, DistMxv);
+	U.ScaleDistMx();
+	U.Run(LINKAGE_Avg, T);
 	}

@@ -112,7 +112,9 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
  *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
  *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_chain_bins, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
- *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
+ *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, mpcgpu_sw_set_scores, mpcgpu_sw_scores and mpcgpu_sw_info (tables, letters,
+ *   work lists and results of the local-alignment scores live in buffers of their own: shard, store, values and the stage-A scratch are
+ *   neither read nor written), and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
  * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
 int mpcgpu_store_epoch(mpcgpu_ctx *ctx, uint64_t *epoch);
@@ -331,6 +333,31 @@ int mpcgpu_align_pairs(mpcgpu_ctx *ctx, uint32_t npairs, const uint32_t *seq1, c
 /* MySparseMx::FromPost (mysparsemx.cpp:115-152) of pair q of the LAST list stage on this context (mpcgpu_align_pairs of at most 256
  * pairs, mpcgpu_align_msas): nnz, offsets[LX+1], values (8 bytes per entry; capacity from a first call with values == NULL). */
 int mpcgpu_get_list_sparse(mpcgpu_ctx *ctx, uint32_t q, uint32_t *nnz, uint32_t *offsets, void *values);
+
+/* ---- guide tree from bare sequences: all-pairs local-alignment scores (kernels_sw.h, mpcgpu_sw.inc) ------------------------
+ * Tables of the score-only Smith-Waterman below. Replaces what MakeBlosum62SMx builds per pair (blosumsmx.cpp:32-53: a letter pair
+ * scores Blosum62_sij[a][b], blosum.cpp:8, when both letters are < 20 and 0 otherwise) and the Open / Ext arguments of SWFast_SMx
+ * (sw.cpp:142-144; -11 and -1 at swdistmx.cpp:106-107). The caller supplies the tables, the library carries no copy of them:
+ *   letter_of_char[256]   g_CharToLetterAmino (alpha.cpp): the letter of every byte value
+ *   alpha, sub            alphabet size (1 .. 32) and alpha x alpha scores, row-major; a letter >= alpha scores 0 against everything
+ *   open, ext             gap scores, both <= 0 (sw.cpp:151-152 asserts the same)
+ * Single context only; the tables stay until the next call or mpcgpu_destroy. */
+int mpcgpu_sw_set_scores(mpcgpu_ctx *ctx, const uint8_t letter_of_char[256], uint32_t alpha, const float *sub, float open,
+                         float ext);
+/* Raw local-alignment scores of a list of pairs of the set given to mpcgpu_set_seqs_registry (or mpcgpu_set_seqs): pair q aligns
+ * seq1[q] with seq2[q]; seq1 == seq2 == NULL means all pairs i < j in InitPairs order (npairs must then be n (n - 1) / 2). Replaces
+ * the value SWFast_Seqs_BLOSUM62 returns (sw.cpp:287-295 -> SWFast_SMx, sw.cpp:142-275) in ThreadBody's loop over all pairs
+ * (swdistmx.cpp:25-85), bit for bit: every cell is the reference's chain of single fp32 adds and maxima. The trace-back
+ * (TraceBackBitSW, sw.cpp:69-140), which feeds only a log line there, is not computed, and no LA x LB matrix exists; the
+ * normalisation by the mean length (swdistmx.cpp:75-76) stays with the caller. Consecutive pairs with the same first sequence and
+ * second sequences q, q + 1, ... are swept as one chain (MPCGPU_SW_CHAIN_COLS columns at most, 8192). The list is cut into batches
+ * of MPCGPU_SW_BATCH pairs (2^24): a result word per pair and a 16-byte item per chain, in device memory of the call's own.
+ * Refused by name before any device work, the context left as it was: scores not set, no sequences, an index outside the set, a
+ * sequence of more than 65 535 positions among those the list names, a pair count that is not n (n - 1) / 2 with NULL lists. */
+int mpcgpu_sw_scores(mpcgpu_ctx *ctx, uint64_t npairs, const uint32_t *seq1, const uint32_t *seq2, float *scores);
+/* The last mpcgpu_sw_scores call: out[0] pairs, out[1] DP cells (sum of LA x LB), out[2] batches, out[3] chains, out[4] chains whose
+ * first sequence is longer than 512 and ran in row blocks, out[5] device time of the kernels in nanoseconds (hipEvents around each batch). */
+int mpcgpu_sw_info(mpcgpu_ctx *ctx, uint64_t out[6]);
 
 /* ---- several GPUs of one node inside ONE process (muscle_amd/csrc/mpcgpu_group.cpp) --------------------------
  * The drop-in binary is one process; it consumes the multi-GPU path through these calls. A group owns one context per

@@ -17,6 +17,7 @@
 #include "kernels_relaxb.h"
 #include "kernels_aln.h"
 #include "kernels_prog.h"
+#include "kernels_sw.h"
 
 #include <algorithm>
 #include <chrono>
@@ -265,6 +266,20 @@ struct mpcgpu_ctx {
 	u64 sa_coop_pairs = 0; u32 sa_coop_waves = 0;    // ... row-block pairs that ran on fb_coop_kernel, and its waves per pair
 	double aa_trace_t[5] = {0, 0, 0, 0, 0}; // MPCGPU_TRACE & 4: host seconds of mpcgpu_align_alns' phases
 	u64 aa_trace_n = 0;
+	// mpcgpu_sw_set_scores / mpcgpu_sw_scores (mpcgpu_sw.inc): tables, buffers of their own, and what mpcgpu_sw_info reports of the last call
+	struct SwState {
+		bool have = false;
+		u8 letter[256];
+		u32 alpha = 0;
+		std::vector<float> sub;
+		float open = 0, ext = 0;
+		DevBuf d_let, d_off, d_tab, d_items, d_scores, d_queue, d_bnd;
+		std::vector<u8> v_let; // (kept: see v_flags above)
+		std::vector<u32> v_off;
+		std::vector<SwItem> v_items;
+		u64 pairs = 0, cells = 0, batches = 0, items = 0, long_items = 0;
+		double ms = 0;
+	} sw;
 };
 
 namespace {
@@ -848,6 +863,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	for (DevBuf *b : {&c->d_rest, &c->d_rest_n, &c->d_res_n, &c->d_nnz_n, &c->d_ea_n, &c->d_flags_n, &c->d_fuse_sort}) b->release();
 	c->d_rects.release(); c->d_need.release(); c->d_exp_klist.release(); c->d_exp_valbase.release();
 	c->d_tiles2.release();
+	for (DevBuf *b : {&c->sw.d_let, &c->sw.d_off, &c->sw.d_tab, &c->sw.d_items, &c->sw.d_scores, &c->sw.d_queue, &c->sw.d_bnd}) b->release();
 	c->pad_seg.release(); release_windows(c);
 	if (c->ev_post) (void)hipEventDestroy(c->ev_post);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -1137,6 +1153,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *c) { return c ? c->npairs : 0; }
 #include "mpcgpu_stage_a.inc"
 #include "mpcgpu_exchange.inc"
 #include "mpcgpu_joins.inc"
+#include "mpcgpu_sw.inc"
 int mpcgpu_relax_info(mpcgpu_ctx *c, char *buf, uint32_t buflen, int *is_fallback)
 {
 	if (!c) return 1;

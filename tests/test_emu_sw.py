@@ -1,0 +1,45 @@
+"""sw_kernel WITHOUT a GPU: the emulator build of the same sources through the checks of tests/_sw.py — the golden bits of the compiled
+reference through mpcgpu_sw_scores, the case table against the restatement bit for bit, refusals by name, other lane orders."""
+import os
+import subprocess
+
+import pytest
+
+import _sw
+
+EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+EMU_LIB = os.path.join(EMU_DIR, "libmpcgpu_emu.so")
+
+
+@pytest.fixture(scope="module")
+def emu():
+    subprocess.check_call(["make", "-C", EMU_DIR], stdout=subprocess.DEVNULL)
+    return EMU_LIB
+
+
+def test_emu_sw_golden_bits(emu):
+    _sw.check_golden(emu)
+
+
+@pytest.mark.parametrize("name", _sw.CASES)
+def test_emu_sw_case(emu, name):
+    _sw.check_case(name, emu)
+
+
+def test_emu_sw_refusals(emu):
+    _sw.check_refusals(emu)
+
+
+@pytest.mark.parametrize("order", ["reverse", "random"])
+def test_emu_sw_other_thread_orders(emu, order):
+    """the fibers of a wave in reverse / shuffled order: a lane that read a neighbour's value before it was handed on would show"""
+    old = os.environ.get("EMU_SCHED")
+    os.environ["EMU_SCHED"] = order
+    try:
+        for name in ("identical", "chain_cut", "explicit_list"):
+            _sw.check_case(name, emu)
+    finally:
+        if old is None:
+            os.environ.pop("EMU_SCHED", None)
+        else:
+            os.environ["EMU_SCHED"] = old
