@@ -112,7 +112,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
  *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
  *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_chain_bins, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
- *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, mpcgpu_sw_set_scores, mpcgpu_sw_scores and mpcgpu_sw_info (tables, letters,
+ *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, mpcgpu_sw_set_scores, mpcgpu_sw_scores, mpcgpu_sw_info and mpcgpu_sw_bins (tables, letters,
  *   work lists and results of the local-alignment scores live in buffers of their own: shard, store, values and the stage-A scratch are
  *   neither read nor written), and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
@@ -358,6 +358,9 @@ int mpcgpu_sw_scores(mpcgpu_ctx *ctx, uint64_t npairs, const uint32_t *seq1, con
 /* The last mpcgpu_sw_scores call: out[0] pairs, out[1] DP cells (sum of LA x LB), out[2] batches, out[3] chains, out[4] chains whose
  * first sequence is longer than 512 and ran in row blocks, out[5] device time of the kernels in nanoseconds (hipEvents around each batch). */
 int mpcgpu_sw_info(mpcgpu_ctx *ctx, uint64_t out[6]);
+/* last mpcgpu_sw_scores call, summed over its batches: per bin b = 1 .. MPC_SW_HMAX + 1 (index 0 unused; bins 1 .. 8: sw_kernel<b> with b
+ * rows per lane, bin 9: the row-block kernel) items[b] = work items of the bin, groups[b] = workgroups launched for it (4 waves each) */
+int mpcgpu_sw_bins(mpcgpu_ctx *ctx, uint64_t items[10], uint64_t groups[10]);
 
 /* ---- several GPUs of one node inside ONE process (muscle_amd/csrc/mpcgpu_group.cpp) --------------------------
  * The drop-in binary is one process; it consumes the multi-GPU path through these calls. A group owns one context per

@@ -266,7 +266,7 @@ struct mpcgpu_ctx {
 	u64 sa_coop_pairs = 0; u32 sa_coop_waves = 0;    // ... row-block pairs that ran on fb_coop_kernel, and its waves per pair
 	double aa_trace_t[5] = {0, 0, 0, 0, 0}; // MPCGPU_TRACE & 4: host seconds of mpcgpu_align_alns' phases
 	u64 aa_trace_n = 0;
-	// mpcgpu_sw_set_scores / mpcgpu_sw_scores (mpcgpu_sw.inc): tables, buffers of their own, and what mpcgpu_sw_info reports of the last call
+	// mpcgpu_sw_set_scores / mpcgpu_sw_scores (mpcgpu_sw.inc): tables, buffers of their own, and what mpcgpu_sw_info / mpcgpu_sw_bins report of the last call
 	struct SwState {
 		bool have = false;
 		u8 letter[256];
@@ -278,6 +278,7 @@ struct mpcgpu_ctx {
 		std::vector<u32> v_off;
 		std::vector<SwItem> v_items;
 		u64 pairs = 0, cells = 0, batches = 0, items = 0, long_items = 0;
+		u64 bin_items[MPC_SW_HMAX + 2] = {}, bin_groups[MPC_SW_HMAX + 2] = {}; // mpcgpu_sw_bins: per bin, summed over the batches
 		double ms = 0;
 	} sw;
 };

@@ -1,4 +1,4 @@
-// mpcgpu_sw.inc — host side of sw_kernel (kernels_sw.h): mpcgpu_sw_set_scores, mpcgpu_sw_scores, mpcgpu_sw_info. Included by mpcgpu.cpp
+// mpcgpu_sw.inc — host side of sw_kernel (kernels_sw.h): mpcgpu_sw_set_scores, mpcgpu_sw_scores, mpcgpu_sw_info, mpcgpu_sw_bins. Included by mpcgpu.cpp
 // inside its extern "C" block. Everything here lives in buffers of its own (mpcgpu_ctx::sw): shard, store and stage-A scratch of the
 // context are neither read nor written, and the store epoch stays where it is.
 
@@ -104,6 +104,7 @@ int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const
 	for (u32 i = 0; i < c->n; ++i) letters += c->len[i];
 	if (letters > 0xffffffffull) return fail(c, "mpcgpu_sw_scores: %llu letters in all, more than a 32-bit offset addresses", (unsigned long long)letters);
 	w.pairs = w.cells = w.batches = w.items = w.long_items = 0;
+	for (u32 b = 0; b < MPC_SW_HMAX + 2; ++b) w.bin_items[b] = w.bin_groups[b] = 0;
 	w.ms = 0.0;
 	if (npairs == 0) return 0;
 	HIPCHK(c, hipSetDevice(c->device));
@@ -179,6 +180,7 @@ int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const
 			const u32 grid = (b == MPC_SW_HMAX + 1) ? long_grid : std::min<u32>((cnt + 3) / 4, cus * 8);
 			launch_sw(b, p, grid, smem, c->stream);
 			HIPCHK(c, hipGetLastError());
+			w.bin_items[b] += cnt; w.bin_groups[b] += grid;
 		}
 		HIPCHK(c, hipEventRecord(eb, c->stream));
 		HIPCHK(c, hipMemcpyAsync(scores + q0, w.d_scores.p, B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -204,5 +206,15 @@ int mpcgpu_sw_info(mpcgpu_ctx *c, uint64_t out[6])
 	const mpcgpu_ctx::SwState &w = c->sw;
 	out[0] = w.pairs; out[1] = w.cells; out[2] = w.batches; out[3] = w.items; out[4] = w.long_items;
 	out[5] = (u64)(w.ms * 1e6); // nanoseconds
+	return 0;
+}
+
+int mpcgpu_sw_bins(mpcgpu_ctx *c, uint64_t items[10], uint64_t groups[10])
+{
+	if (!c) return 1;
+	if (!items || !groups) return fail(c, "mpcgpu_sw_bins: NULL argument");
+	static_assert(MPC_SW_HMAX + 2 == 10, "mpcgpu_sw_bins reports bins 0 .. MPC_SW_HMAX + 1");
+	const mpcgpu_ctx::SwState &w = c->sw;
+	for (u32 b = 0; b < MPC_SW_HMAX + 2; ++b) { items[b] = w.bin_items[b]; groups[b] = w.bin_groups[b]; }
 	return 0;
 }

@@ -24,13 +24,23 @@ DROPIN = os.path.join(GOLDEN_DIR, "sw_dropin.json")
 # kernels_sw.h: rows per lane up to MPC_SW_HMAX = 8 (a bin per 64 rows), row blocks of 512 rows beyond
 LANE = 64
 BLOCK_ROWS = 512
+NBINS = 10  # mpcgpu_sw_bins: bins 1 .. 8 = rows per lane, bin 9 = the row-block kernel (index 0 unused)
+LONG_BIN = 9
 # drop-in sets: name -> (sequences, family length, seed, extra arguments of -super7)
-DROPIN_SETS = {"swx_12x40": (12, 40, 21, []), "swx_20x30_b6": (20, 30, 22, ["-shrub_size", "6"])}
+DROPIN_SETS = {"swx_12x40": (12, 40, 21, []), "swx_20x30_b6": (20, 30, 22, ["-shrub_size", "6"]),
+               "swx_8x560_b4": (8, 560, 23, ["-shrub_size", "4"])}
+# ... cut to these lengths (before the X): as row sequences the row-block kernel twice and the bins 2, 3, 5, 6 and 8; the last sequence
+# is a column only
+DROPIN_CUTS = {"swx_8x560_b4": [550, 110, 530, 180, 300, 360, 450, 480]}
 
 
 def dropin_seqs(name, terminated=True):
     n, L, seed, _ = DROPIN_SETS[name]
-    return [s + ("X" if terminated else "") for s in make_family(n, L, seed=seed)]
+    fam = make_family(n, L, seed=seed)
+    if name in DROPIN_CUTS:
+        assert all(len(s) >= c for s, c in zip(fam, DROPIN_CUTS[name])), [len(s) for s in fam]
+        fam = [s[:c] for s, c in zip(fam, DROPIN_CUTS[name])]
+    return [s + ("X" if terminated else "") for s in fam]
 
 
 def golden_input():
@@ -106,6 +116,22 @@ def sw_ref(a, b, loc=None, sub=None, open_score=None, ext_score=None):
 
 
 # ---- the case table -----------------------------------------------------------------------------------------------------------
+LONG_CHAIN_LENS = [600, 40, 513, 70, 1025, 33, 520]
+# column sequences of "long_chain_separators": the run the rows are swept against first, and a second run whose separators fall on
+# columns 63, 128 and 193 of the item (63, 64 and 65 modulo 64: the last column of a 64-column chunk and the first two of the next)
+SEPARATOR_RUNS = ([1, 1, 2, 63, 64, 65, 1, 130], [63, 64, 64, 1, 1, 62])
+
+
+def separator_columns(run):
+    """columns of the separators on the column axis of an item that holds the sequences of these lengths"""
+    out, at = [], 0
+    for L in run:
+        at += L
+        out.append(at)
+        at += 1
+    return out
+
+
 def _rand(L, seed, alphabet=AMINO):
     rng = np.random.default_rng(seed)
     return "".join(alphabet[int(k)] for k in rng.integers(0, len(alphabet), L))
@@ -162,6 +188,25 @@ def case(name):
         s1 = [3, 3, 3, 0, 8, 8, 2, 2, 2, 2, 5, 1, 1]
         s2 = [4, 5, 6, 0, 1, 1, 7, 8, 3, 4, 2, 0, 1]
         return seqs, s1, s2, {}
+    if name in ("long_chains", "long_chains_cols1", "long_chains_batch4"):
+        # all pairs of long and short rows in turn: the row-block items hold 6, 4 and 2 pairs (one each with one column sequence per item;
+        # batches of 4 pairs cut the chains)
+        base = _rand(1025, 61)
+        seqs = [_mutate(base[:L], 300 + L) for L in LONG_CHAIN_LENS]
+        env = {"long_chains": {}, "long_chains_cols1": {"MPCGPU_SW_CHAIN_COLS": "1"}, "long_chains_batch4": {"MPCGPU_SW_BATCH": "4"}}[name]
+        return seqs, None, None, env
+    if name.startswith("long_chain_separators"):
+        # a row sequence of several row blocks against two runs of consecutive column sequences: the separator columns of the first run
+        # lie back to back and behind sequences of 63, 64 and 65 columns, those of the second at columns 63, 64 and 65 of a 64-column
+        # chunk of the item's column axis. The row sequence once below and once above its columns in the set.
+        LA = {"": 1025, "_513": 513, "_1024": 1024, "_1536": 1536}[name[len("long_chain_separators"):]]
+        base = _rand(1536, 62)
+        row = _mutate(base[:LA], 63)
+        cols = [_mutate(base[40 * k:40 * k + L], 400 + k) for k, L in enumerate(SEPARATOR_RUNS[0] + SEPARATOR_RUNS[1])]
+        n0, n1 = len(SEPARATOR_RUNS[0]), len(SEPARATOR_RUNS[1])
+        hi = 1 + n0 + n1
+        run0, run1 = list(range(1, 1 + n0)), list(range(1 + n0, hi))
+        return [row] + cols + [row], [0] * n0 + [hi] * n0 + [0] * n1 + [hi] * n1, run0 + run0 + run1 + run1, {}
     if name == "long_5000":  # device only
         base = _rand(5000, 51)
         return [base, _mutate(base, 52, 0.4)], [0], [1], {}
@@ -172,25 +217,88 @@ def case(name):
 
 
 CASES = ["len_1_2", "no_positive_cell", "wildcards", "lower_and_other_bytes", "identical", "lane_bins", "row_blocks", "ragged_all_pairs",
-         "batch_cut", "chain_cut", "explicit_list"]
+         "batch_cut", "chain_cut", "explicit_list", "long_chains", "long_chains_cols1", "long_chains_batch4", "long_chain_separators",
+         "long_chain_separators_513", "long_chain_separators_1024", "long_chain_separators_1536"]
 GPU_ONLY = ["long_5000", "long_30x20000"]
+
+
+def pair_list(n, s1=None, s2=None):
+    """the pairs of a call: the lists, or all pairs i < j in InitPairs order"""
+    if s1 is None:
+        return [(i, j) for i in range(n) for j in range(i + 1, n)]
+    return [(int(a), int(b)) for a, b in zip(s1, s2)]
+
+
+_REF_MEMO = {}
+
+
+def want_scores(seqs, s1=None, s2=None, tab=None):
+    """sw_ref of every pair of the call, computed once per distinct (row sequence, column sequence, tables): big lists are built from
+    few distinct sequences. tab = (key, letter_of_char, sub, open, ext) or None for the reference's tables."""
+    key, args = (None, ()) if tab is None else (tab[0], tab[1:])
+    pairs = pair_list(len(seqs), s1, s2)
+    out = np.zeros(len(pairs), np.float32)
+    for q, (i, j) in enumerate(pairs):
+        k = (seqs[i], seqs[j], key)
+        if k not in _REF_MEMO:
+            _REF_MEMO[k] = sw_ref(seqs[i], seqs[j], *args)
+        out[q] = _REF_MEMO[k]
+    out.setflags(write=False)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
 def expected(name):
     seqs, s1, s2, _ = case(name)
-    if s1 is None:
-        pairs = [(i, j) for i in range(len(seqs)) for j in range(i + 1, len(seqs))]
-    else:
-        pairs = list(zip(s1, s2))
-    memo = {}
-    out = np.zeros(len(pairs), np.float32)
-    for q, (i, j) in enumerate(pairs):
-        if (i, j) not in memo:
-            memo[(i, j)] = sw_ref(seqs[i], seqs[j])
-        out[q] = memo[(i, j)]
-    out.setflags(write=False)
-    return out
+    return want_scores(seqs, s1, s2)
+
+
+def predict(lens, s1=None, s2=None, env=None):
+    """The plan of mpcgpu_sw_scores (mpcgpu_sw.inc) restated from its rule. The list is cut into batches of MPCGPU_SW_BATCH pairs
+    (2^24). Inside a batch a pair joins the item before it when it has the same row sequence, its column sequence is the next one of
+    the set (y == previous y + 1) and the item's columns (every column sequence and its separator) stay within MPCGPU_SW_CHAIN_COLS
+    (8192); otherwise it opens an item, and an item never crosses a batch. An item's bin is the rows per lane of its row sequence,
+    ceil(L / 64) for L <= 512, and bin 9 (the row-block kernel) beyond.
+    -> items: per bin, summed over the batches; batches; long_items; chains: (batch, bin, row sequence, pairs, columns) per item in
+    list order; batch_items: per batch the items of every bin."""
+    env = env or {}
+    batch_cap = max(1, int(env.get("MPCGPU_SW_BATCH", 1 << 24)))
+    chain_cols = max(1, int(env.get("MPCGPU_SW_CHAIN_COLS", 8192)))
+    pairs = pair_list(len(lens), s1, s2)
+    chains, batch_items = [], []
+    for nb, q0 in enumerate(range(0, len(pairs), batch_cap)):
+        cur, prev_y = None, None
+        count = [0] * NBINS
+        for x, y in pairs[q0:q0 + batch_cap]:
+            cols = int(lens[y]) + 1
+            if cur is not None and cur[2] == x and y == prev_y + 1 and cur[4] + cols <= chain_cols:
+                cur[3] += 1
+                cur[4] += cols
+            else:
+                lx = int(lens[x])
+                cur = [nb, (lx + LANE - 1) // LANE if lx <= BLOCK_ROWS else LONG_BIN, x, 1, cols]
+                chains.append(cur)
+                count[cur[1]] += 1
+            prev_y = y
+        batch_items.append(count)
+    items = [sum(b[k] for b in batch_items) for k in range(NBINS)]
+    return {"items": items, "batches": len(batch_items), "long_items": items[LONG_BIN], "chains": [tuple(c) for c in chains],
+            "batch_items": batch_items}
+
+
+def check_plan(g, pr, tag=""):
+    """sw_info() and sw_bins() of the last call against the restated plan: the items of every bin exactly; the workgroups of a bin
+    between one per batch that has items of the bin and one per four items (the library takes the smaller of that and a multiple of
+    the device's CUs, which the plan does not know)"""
+    info = g.sw_info()
+    items, groups = g.sw_bins()
+    assert list(items) == pr["items"], (tag, items, pr["items"])
+    assert info[2] == pr["batches"] and info[3] == sum(pr["items"]) and info[4] == pr["long_items"], (tag, info, pr["items"], pr["batches"])
+    for b in range(NBINS):
+        lo = sum(1 for c in pr["batch_items"] if c[b])
+        hi = sum((c[b] + 3) // 4 for c in pr["batch_items"])
+        assert lo <= groups[b] <= hi, (tag, b, groups, lo, hi)
+    return items, groups
 
 
 def bits(a):
@@ -229,6 +337,7 @@ def check_golden(lib_path=None):
         n = len(gd["seqs"])
         info = g.sw_info()
         assert info[0] == n * (n - 1) // 2 and info[2] == 1 and info[4] == 0, info
+        check_plan(g, predict([len(x) for x in gd["seqs"]]), "golden")
         # symmetric in (A, B): the transposed list gives the same bits
         s1 = [j for i in range(n) for j in range(i + 1, n)]
         s2 = [i for i in range(n) for j in range(i + 1, n)]
@@ -257,6 +366,19 @@ def check_case(name, lib_path=None):
             assert info[4] == 6, info
         if name in ("lane_bins", "ragged_all_pairs"):
             assert info[4] == 0, info
+        # the routes: every bin's items as the restated plan has them
+        pr = predict([len(x) for x in seqs], s1, s2, env)
+        items, groups = check_plan(g, pr, name)
+        if name == "lane_bins":  # every sw_kernel<H, false> was launched, the row-block kernel was not
+            assert all(items[h] >= 1 and groups[h] >= 1 for h in range(1, 9)) and items[LONG_BIN] == 0 and groups[LONG_BIN] == 0, (items, groups)
+        if name == "row_blocks":
+            assert items[LONG_BIN] == 6 and groups[LONG_BIN] >= 1, (items, groups)
+        if name == "long_chains":
+            assert sorted(c[3] for c in pr["chains"] if c[1] == LONG_BIN) == [2, 4, 6] and items[LONG_BIN] == 3, pr["chains"]
+        if name == "long_chains_cols1":
+            assert items[LONG_BIN] == 12 and sum(items) == len(want), items
+        if name.startswith("long_chain_separators"):
+            assert items[LONG_BIN] == 4 and sum(items) == 4, items
     finally:
         g.close()
 
@@ -290,3 +412,191 @@ def check_refusals(lib_path=None):
             assert g.store_epoch() == ep
     finally:
         g.close()
+
+
+# ---- a wave that takes a second item ------------------------------------------------------------------------------------------
+QUEUE_CUS = 304  # the lists of size "gpu" give every wave of a device of up to this many CUs a second item
+
+
+def queue_reuse_bin1(n):
+    """all pairs of n sequences of 3 .. 8 residues (twelve distinct ones in turn), one pair per item: n (n - 1) / 2 items of bin 1"""
+    distinct = [_rand(3 + k % 6, 80 + k) for k in range(12)]
+    return [distinct[k % 12] for k in range(n)], None, None, {"MPCGPU_SW_CHAIN_COLS": "1"}
+
+
+def queue_reuse_long(count):
+    """count items of the row-block bin, none a chain: item q pairs row sequence q mod 6 (513 .. 530 residues) with column sequence q mod 8
+    (4 and 90 residues in turn), so the row sequence changes from every item to the next and neighbouring items differ in their columns"""
+    base = _rand(530, 90)
+    rows = [_mutate(base[:L], 500 + L) for L in (513, 516, 520, 523, 527, 530)]
+    cols = [_mutate(base[100 + k:100 + k + (4, 90)[k % 2]], 600 + k) for k in range(8)]
+    return rows + cols, [q % 6 for q in range(count)], [6 + q % 8 for q in range(count)], {}
+
+
+def queue_reuse_sizes(size, lib_path=None):
+    """-> (sequences of the bin-1 list, items of the row-block list). "gpu": for up to QUEUE_CUS CUs — more than 8 x 4 x 304 = 9 728
+    items of bin 1 and more than 2 x 4 x 304 = 2 432 of the row-block bin. "emu": the smallest lists for the CUs the emulator reports,
+    read from the workgroups of a first call whose (items + 3) / 4 lies above the grid's limit of 8 per CU."""
+    if size == "gpu":
+        return 150, 2600
+    seqs, s1, s2, env = queue_reuse_bin1(24)
+    g = context(seqs, lib_path)
+    try:
+        got = _with_env(env, lambda: g.sw_scores(s1, s2))
+        assert np.array_equal(bits(got), bits(want_scores(seqs, s1, s2)))
+        items, groups = g.sw_bins()
+    finally:
+        g.close()
+    assert items[1] == 276 and groups[1] < 69 and groups[1] % 8 == 0, ("the first call did not reach the grid's limit", items, groups)
+    cus = groups[1] // 8
+    n = 2
+    while n * (n - 1) // 2 <= 4 * 8 * cus:
+        n += 1
+    return n, 4 * 2 * cus + 1
+
+
+def check_queue_reuse(size, lib_path=None):
+    n, count = queue_reuse_sizes(size, lib_path)
+    for what, b, (seqs, s1, s2, env) in (("bin 1", 1, queue_reuse_bin1(n)), ("row blocks", LONG_BIN, queue_reuse_long(count))):
+        want = want_scores(seqs, s1, s2)
+        g = context(seqs, lib_path)
+        try:
+            got = _with_env(env, lambda: g.sw_scores(s1, s2))
+            bad = np.nonzero(bits(got) != bits(want))[0]
+            assert len(bad) == 0, (what, bad[:10], got[bad[:10]], want[bad[:10]])
+            items, groups = check_plan(g, predict([len(x) for x in seqs], s1, s2, env), what)
+            assert items[b] == len(want) and sum(items) == len(want), (what, items)
+            # four waves per workgroup: more items than waves, so at least one wave went back to the queue and took a second item
+            assert items[b] > 4 * groups[b], "%s: %d items for %d workgroups of 4 waves — no wave is certain to have taken a second item " \
+                "(a device of more than %d CUs needs longer lists)" % (what, items[b], groups[b], QUEUE_CUS)
+        finally:
+            g.close()
+
+
+# ---- tables other than BLOSUM62 / -11 / -1 -----------------------------------------------------------------------------------
+TABLES = [(1, 0.0, 0.0, True), (32, -0.3, -0.7, True), (4, -2.5, 0.0, False), (20, 0.0, -1.0, True), (20, -1.0, -11.0, True)]  # alpha, open, ext, symmetric
+
+
+@functools.lru_cache(maxsize=None)
+def table_case(k):
+    """-> (tab = (key, letter_of_char, sub, open, ext), sequences) for TABLES[k]: a seeded random substitution table with a positive
+    diagonal, byte 'A' + l for letter l and the wildcard for every other byte, sequences of 5, 70, 130, 600 and 31 letters 0 .. alpha
+    (the wildcard included)"""
+    alpha, op, ex, symmetric = TABLES[k]
+    rng = np.random.default_rng(700 + k)
+    sub = rng.uniform(-5.0, 3.0, (alpha, alpha)).astype(np.float32)
+    if symmetric:
+        sub = np.triu(sub) + np.triu(sub, 1).T
+    sub[np.diag_indices(alpha)] = np.abs(sub[np.diag_indices(alpha)]) + np.float32(0.5)
+    loc = np.full(256, alpha, np.uint8)
+    loc[ord("A"):ord("A") + alpha] = np.arange(alpha)
+    chars = [chr(ord("A") + l) for l in range(alpha)] + ["~"]
+    seqs = ["".join(chars[int(l)] for l in rng.integers(0, alpha + 1, L)) for L in (5, 70, 130, 600, 31)]
+    sub.setflags(write=False)
+    return ("table%d" % k, loc, sub, op, ex), seqs
+
+
+def check_tables(lib_path=None):
+    """one context, one table after the other: every call scores with the tables set last"""
+    g = None
+    try:
+        for k, (alpha, op, ex, symmetric) in enumerate(TABLES):
+            tab, seqs = table_case(k)
+            if g is None:
+                g = context(seqs, lib_path, scores=False)
+            else:
+                g.set_seqs_registry(seqs)
+            g.sw_set_scores(*tab[1:])
+            n = len(seqs)
+            lists = [(None, None)]
+            if not symmetric:  # score(A, B) != score(B, A): the transposed list too
+                pairs = pair_list(n)
+                lists.append(([j for i, j in pairs], [i for i, j in pairs]))
+            for s1, s2 in lists:
+                got = g.sw_scores(s1, s2)
+                want = want_scores(seqs, s1, s2, tab)
+                bad = np.nonzero(bits(got) != bits(want))[0]
+                assert len(bad) == 0, (TABLES[k], s1 is None, bad[:10], got[bad[:10]], want[bad[:10]])
+                check_plan(g, predict([len(x) for x in seqs], s1, s2), TABLES[k])
+        # back to the first table on the same context and the same sequences
+        tab = table_case(0)[0]
+        g.sw_set_scores(*tab[1:])
+        assert np.array_equal(bits(g.sw_scores()), bits(want_scores(seqs, None, None, tab)))
+    finally:
+        if g is not None:
+            g.close()
+
+
+# ---- reuse of a context -------------------------------------------------------------------------------------------------------
+def check_context_reuse(lib_path=None):
+    """sets of fewer, more and longer sequences in turn on one context, through mpcgpu_set_seqs_registry and through mpcgpu_set_seqs:
+    a call with a row-block bin after one without and the reverse; the buffers of the larger call stay"""
+    fam = make_family(12, 64, seed=71)
+    A = [s[:L] for s, L in zip(fam, [60, 7, 33, 58, 1, 45, 60, 12, 29, 51, 3, 40])]
+    base = _rand(700, 72)
+    B = [_mutate(base[:80], 73), base, _mutate(base[300:330], 74), _mutate(base[100:300], 75)]
+    s, t, m, i, thr = G.hmm_tables()
+    g = MpcGpu(0, lib_path)
+    try:
+        g.set_hmm(s, t, m, i, thr)
+        g.sw_set_scores(*tables())
+        first = None
+        for setter in (g.set_seqs_registry, g.set_seqs):
+            for seqs in (A, B, A):
+                setter(seqs)
+                got = g.sw_scores()
+                want = want_scores(seqs)
+                bad = np.nonzero(bits(got) != bits(want))[0]
+                assert len(bad) == 0, (setter.__name__, len(seqs), bad[:10], got[bad[:10]], want[bad[:10]])
+                items, _ = check_plan(g, predict([len(x) for x in seqs]), (setter.__name__, len(seqs)))
+                assert (items[LONG_BIN] > 0) == (seqs is B), items
+                if seqs is A:  # the bits of the first call, whatever ran in between
+                    first = got.copy() if first is None else first
+                    assert np.array_equal(bits(got), bits(first))
+    finally:
+        g.close()
+
+
+# ---- beside the posterior stage -----------------------------------------------------------------------------------------------
+def check_beside_the_stage(lib_path=None):
+    """mpcgpu_sw_scores between mpcgpu_build_store and the relax iterations: shard, store and values are what the oracle has, the store
+    epoch moves as on a context without the call, and the scores are the restatement's"""
+    import _parity as P
+    seqs = make_family(8, 50, seed=77)
+    want = P.run_oracle(seqs, iters=2)
+    s, t, m, i, thr = G.hmm_tables()
+
+    def run(with_sw):
+        g = MpcGpu(0, lib_path)
+        try:
+            g.set_hmm(s, t, m, i, thr)
+            g.set_seqs(seqs)
+            g.calc_posteriors()
+            g.build_store()
+            epochs = [g.store_epoch()]
+            scores = None
+            if with_sw:
+                g.sw_set_scores(*tables())
+                scores = g.sw_scores()
+                assert g.store_epoch() == epochs[0]
+                check_plan(g, predict([len(x) for x in seqs]), "beside the stage")
+            ea = g.get_ea().copy()
+            stages, nnz = [g.get_sparse_range()], [g.get_nnz().copy()]
+            for _ in range(2):
+                g.cons_iter()
+                epochs.append(g.store_epoch())
+                g.cons_commit()
+                epochs.append(g.store_epoch())
+                stages.append(g.get_sparse_range())
+                nnz.append(g.get_nnz().copy())
+            return stages, ea, nnz, epochs, scores
+        finally:
+            g.close()
+    stages, ea, nnz, epochs, scores = run(True)
+    P.assert_same((stages, ea), want, "store and values around mpcgpu_sw_scores")
+    for st, z in zip(want[0], nnz):
+        assert [len(v) // 2 for _, v in st] == z.tolist()
+    assert np.array_equal(bits(scores), bits(want_scores(seqs)))
+    stages0, ea0, nnz0, epochs0, _ = run(False)
+    assert epochs == epochs0 and epochs[-1] > epochs[0], (epochs, epochs0)
+    P.assert_same((stages0, ea0), want, "the same context without the call")
