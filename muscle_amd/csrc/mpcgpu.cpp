@@ -30,6 +30,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -408,248 +409,120 @@ void ensure_dyn_smem(const void *fn, size_t smem)
 	else (void)hipGetLastError();
 }
 
-template <int H, bool MEGA, bool LONG = false> void launch_fb(const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
+// ---- the forward/backward kernel families (kernels_fb.h, kernels_fbc.h, kernels_fbcoop.h): symbols, occupancy, launches --------
+// A run-time H (rows per lane, 1 .. MPC_HMAX) as a compile-time constant: returns f(std::integral_constant<int, H>()); for any other H
+// f is not called and the result is a value-initialised one (nullptr, 0, nothing).
+template <class F> auto with_h(int H, F &&f) -> decltype(f(std::integral_constant<int, 1>()))
 {
-	auto kern = fb_kernel<H, MEGA, LONG>;
-	ensure_dyn_smem((const void *)kern, smem);
-	MPC_LAUNCH(kern, grid, block, smem, st, p);
-}
-
-template <int H, bool MEGA, bool LONG = false> int occ_fb(u32 block, size_t smem)
-{
-	int nb = 0;
-	ensure_dyn_smem((const void *)fb_kernel<H, MEGA, LONG>, smem);
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fb_kernel<H, MEGA, LONG>, (int)block, smem) != hipSuccess || nb < 1)
-		nb = 1;
-	return nb;
+	static_assert(MPC_HMAX == 16, "one case per H");
+	switch (H) {
+#define MPC_CASE(h) case h: return f(std::integral_constant<int, h>());
+	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
+	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
+#undef MPC_CASE
+	default: return decltype(f(std::integral_constant<int, 1>()))();
+	}
 }
 
 // Row-block kernels (sequences X longer than 64*MPC_HMAX): H = MPC_LONG_H rows per lane; H = 1 exists so that
 // tests reach several blocks with short sequences (MPCGPU_FB_LONG_H=1 MPCGPU_FB_LONG_MIN=<rows>).
 #define MPC_LONG_H 7
 #define MPC_LONG_H_SMALL 4 // 166 VGPRs (3 waves per SIMD) where H = 7 needs 217 (2): used when memory lets more than 2 waves per SIMD be resident
-int occ_fb_long(int H, bool mega, u32 block, size_t smem)
+// ... the same for their three values of H (any other H: MPC_LONG_H)
+template <class F> auto with_long_h(int H, F &&f) -> decltype(f(std::integral_constant<int, 1>()))
 {
-	if (H == 1) return mega ? occ_fb<1, true, true>(block, smem) : occ_fb<1, false, true>(block, smem);
-	if (H == MPC_LONG_H_SMALL) return mega ? occ_fb<MPC_LONG_H_SMALL, true, true>(block, smem) : occ_fb<MPC_LONG_H_SMALL, false, true>(block, smem);
-	return mega ? occ_fb<MPC_LONG_H, true, true>(block, smem) : occ_fb<MPC_LONG_H, false, true>(block, smem);
+	if (H == 1) return f(std::integral_constant<int, 1>());
+	if (H == MPC_LONG_H_SMALL) return f(std::integral_constant<int, MPC_LONG_H_SMALL>());
+	return f(std::integral_constant<int, MPC_LONG_H>());
+}
+#define MPC_H decltype(h)::value // inside the generic lambdas below
+
+// the kernel of a family for (H, mega[, row blocks]); nullptr: no such instantiation
+const void *fb_fn(int H, bool mega, bool lng = false)
+{
+	if (lng) return with_long_h(H, [&](auto h) { return mega ? (const void *)fb_kernel<MPC_H, true, true> : (const void *)fb_kernel<MPC_H, false, true>; });
+	return with_h(H, [&](auto h) { return mega ? (const void *)fb_kernel<MPC_H, true, false> : (const void *)fb_kernel<MPC_H, false, false>; });
+}
+const void *fb_coop_fn(int H, bool mega)
+{
+	return with_long_h(H, [&](auto h) { return mega ? (const void *)fb_coop_kernel<MPC_H, true> : (const void *)fb_coop_kernel<MPC_H, false>; });
+}
+const void *fbc_fn(int H, bool mega)
+{
+	return with_h(H, [&](auto h) { return mega ? (const void *)fb_chain_mega_kernel<MPC_H> : (const void *)fb_chain_kernel<MPC_H>; });
+}
+const void *fbcp_fn(int H)
+{
+	return with_h(H, [&](auto h) { return (const void *)fb_chain_post_kernel<MPC_H>; });
 }
 
-void launch_fb_long(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	if (H == 1) { if (mega) launch_fb<1, true, true>(p, grid, block, smem, st); else launch_fb<1, false, true>(p, grid, block, smem, st); }
-	else if (H == MPC_LONG_H_SMALL) { if (mega) launch_fb<MPC_LONG_H_SMALL, true, true>(p, grid, block, smem, st); else launch_fb<MPC_LONG_H_SMALL, false, true>(p, grid, block, smem, st); }
-	else if (mega) launch_fb<MPC_LONG_H, true, true>(p, grid, block, smem, st);
-	else launch_fb<MPC_LONG_H, false, true>(p, grid, block, smem, st);
-}
-
-// fb_coop_kernel (kernels_fbcoop.h): the row-block sweep with the waves of a workgroup on one pair. smem includes MPC_FB_COOP_LDS_BYTES.
-template <int H, bool MEGA> void launch_fb_coop_t(const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	auto kern = fb_coop_kernel<H, MEGA>;
-	ensure_dyn_smem((const void *)kern, smem);
-	MPC_LAUNCH(kern, grid, block, smem, st, p);
-}
-
-template <int H, bool MEGA> int occ_fb_coop_t(u32 block, size_t smem)
+// workgroups of `block` threads a CU keeps resident, as the runtime reports them (0: such a workgroup does not fit, no answer, or no kernel)
+int occ_blocks(const void *fn, u32 block, size_t smem)
 {
 	int nb = 0;
-	ensure_dyn_smem((const void *)fb_coop_kernel<H, MEGA>, smem);
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fb_coop_kernel<H, MEGA>, (int)block, smem) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
-	return nb;
-}
-
-// workgroups of `block` threads a CU keeps resident (0: such a workgroup does not fit)
-int occ_fb_coop(int H, bool mega, u32 block, size_t smem)
-{
-	if (H == 1) return mega ? occ_fb_coop_t<1, true>(block, smem) : occ_fb_coop_t<1, false>(block, smem);
-	if (H == MPC_LONG_H_SMALL) return mega ? occ_fb_coop_t<MPC_LONG_H_SMALL, true>(block, smem) : occ_fb_coop_t<MPC_LONG_H_SMALL, false>(block, smem);
-	return mega ? occ_fb_coop_t<MPC_LONG_H, true>(block, smem) : occ_fb_coop_t<MPC_LONG_H, false>(block, smem);
-}
-
-// waves per workgroup the instantiation is compiled for
-u32 fb_coop_wave_limit(int H, bool mega)
-{
-	if (H == 1) return (u32)(mega ? FbCoopBounds<1, true>::threads : FbCoopBounds<1, false>::threads) / 64;
-	if (H == MPC_LONG_H_SMALL) return (u32)(mega ? FbCoopBounds<MPC_LONG_H_SMALL, true>::threads : FbCoopBounds<MPC_LONG_H_SMALL, false>::threads) / 64;
-	return (u32)(mega ? FbCoopBounds<MPC_LONG_H, true>::threads : FbCoopBounds<MPC_LONG_H, false>::threads) / 64;
-}
-
-void launch_fb_coop(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	if (H == 1) { if (mega) launch_fb_coop_t<1, true>(p, grid, block, smem, st); else launch_fb_coop_t<1, false>(p, grid, block, smem, st); }
-	else if (H == MPC_LONG_H_SMALL) { if (mega) launch_fb_coop_t<MPC_LONG_H_SMALL, true>(p, grid, block, smem, st); else launch_fb_coop_t<MPC_LONG_H_SMALL, false>(p, grid, block, smem, st); }
-	else if (mega) launch_fb_coop_t<MPC_LONG_H, true>(p, grid, block, smem, st);
-	else launch_fb_coop_t<MPC_LONG_H, false>(p, grid, block, smem, st);
-}
-
-int occ_fb_h(int H, bool mega, u32 block, size_t smem)
-{
-	switch (H) {
-#define MPC_CASE(h) case h: return mega ? occ_fb<h, true>(block, smem) : occ_fb<h, false>(block, smem);
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: return 1;
-	}
-}
-
-void launch_fb_h(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	switch (H) {
-#define MPC_CASE(h) case h: if (mega) launch_fb<h, true>(p, grid, block, smem, st); else launch_fb<h, false>(p, grid, block, smem, st); break;
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: break;
-	}
-}
-
-// fb_chain_kernel / fb_chain_mega_kernel (kernels_fbc.h): chains of pairs that share their row sequence; MEGA: structure-profile emissions
-template <int H, bool MEGA> void launch_fbc(const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	if (MEGA) {
-		auto kern = fb_chain_mega_kernel<H>;
-		ensure_dyn_smem((const void *)kern, smem);
-		MPC_LAUNCH(kern, grid, block, smem, st, p);
-	} else {
-		auto kern = fb_chain_kernel<H>;
-		ensure_dyn_smem((const void *)kern, smem);
-		MPC_LAUNCH(kern, grid, block, smem, st, p);
-	}
-}
-
-// workgroups a CU keeps resident, as the runtime reports them (0: such a workgroup does not fit, or no answer)
-template <int H, bool MEGA> int occ_fbc_raw(u32 block, size_t smem)
-{
-	int nb = 0;
-	const void *fn = MEGA ? (const void *)fb_chain_mega_kernel<H> : (const void *)fb_chain_kernel<H>;
+	if (!fn) return 0;
 	ensure_dyn_smem(fn, smem);
 	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)block, smem) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
 	return nb < 0 ? 0 : nb;
 }
-
 // ... for sizing grids and planes: at least 1
-int occ_fbc_h(int H, bool mega, u32 block, size_t smem)
+int occ_fb_h(int H, bool mega, u32 block, size_t smem) { return std::max(occ_blocks(fb_fn(H, mega), block, smem), 1); }
+int occ_fb_long(int H, bool mega, u32 block, size_t smem) { return std::max(occ_blocks(fb_fn(H, mega, true), block, smem), 1); }
+int occ_fbc_h(int H, bool mega, u32 block, size_t smem) { return std::max(occ_blocks(fbc_fn(H, mega), block, smem), 1); }
+// ... unclamped (0: does not fit). smem of fb_coop_kernel includes MPC_FB_COOP_LDS_BYTES, that of fb_chain_post_kernel the waves' finishing
+// slices; chain_plan compares fb_chain_mega_kernel<H>'s with fb_kernel<H, true>'s and drops a bin whose workgroup does not fit
+int occ_fb_coop(int H, bool mega, u32 block, size_t smem) { return occ_blocks(fb_coop_fn(H, mega), block, smem); }
+int occ_fbcm_fit_h(int H, u32 block, size_t smem) { return occ_blocks(fbc_fn(H, true), block, smem); }
+int occ_fbcp_h(int H, u32 block, size_t smem) { return occ_blocks(fbcp_fn(H), block, smem); }
+
+// waves per workgroup the fb_coop_kernel instantiation is compiled for
+u32 fb_coop_wave_limit(int H, bool mega)
 {
-	int nb = 0;
-	switch (H) {
-#define MPC_CASE(h) case h: nb = mega ? occ_fbc_raw<h, true>(block, smem) : occ_fbc_raw<h, false>(block, smem); break;
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: break;
-	}
-	return nb < 1 ? 1 : nb;
+	return with_long_h(H, [&](auto h) { return (u32)(mega ? FbCoopBounds<MPC_H, true>::threads : FbCoopBounds<MPC_H, false>::threads) / 64; });
 }
 
-// ... of fb_chain_mega_kernel<H>, unclamped: chain_plan compares it with fb_kernel<H, true>'s and drops a bin whose workgroup does not fit
-int occ_fbcm_fit_h(int H, u32 block, size_t smem)
-{
-	switch (H) {
-#define MPC_CASE(h) case h: return occ_fbc_raw<h, true>(block, smem);
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: return 0;
-	}
-}
-
-// does fb_chain_mega_kernel<H> keep values in scratch memory (the register allocator spilled)? The emulator has no registers to run out of.
-template <int H> bool fbcm_spills()
+// does the kernel keep values in scratch memory (the register allocator spilled)? The emulator has no registers to run out of; no such
+// kernel, or no answer, counts as spilling.
+bool kernel_spills(const void *fn)
 {
 #ifdef MPC_EMU
-	return false;
+	return !fn;
 #else
 	hipFuncAttributes a;
-	if (hipFuncGetAttributes(&a, (const void *)fb_chain_mega_kernel<H>) != hipSuccess) { (void)hipGetLastError(); return true; }
+	if (!fn || hipFuncGetAttributes(&a, fn) != hipSuccess) { (void)hipGetLastError(); return true; }
 	return a.localSizeBytes != 0;
 #endif
 }
+bool fbcm_spills_h(int H) { return kernel_spills(fbc_fn(H, true)); }
+bool fbcp_spills_h(int H) { return kernel_spills(fbcp_fn(H)); }
 
-bool fbcm_spills_h(int H)
+template <class K, class P> void launch_kernel(K kern, const P &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-	switch (H) {
-#define MPC_CASE(h) case h: return fbcm_spills<h>();
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: return true;
-	}
-}
-
-void launch_fbc_h(int H, bool mega, const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	switch (H) {
-#define MPC_CASE(h) case h: if (mega) launch_fbc<h, true>(p, grid, block, smem, st); else launch_fbc<h, false>(p, grid, block, smem, st); break;
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: break;
-	}
-}
-
-// fb_chain_post_kernel (kernels_fbc.h): the chain sweeps with every chain's pairs finished in place. smem includes the waves' finishing slices.
-template <int H> void launch_fbcp(const FbChainPostParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
-{
-	auto kern = fb_chain_post_kernel<H>;
 	ensure_dyn_smem((const void *)kern, smem);
 	MPC_LAUNCH(kern, grid, block, smem, st, p);
 }
-
-// workgroups a CU keeps resident (0: such a workgroup does not fit)
-template <int H> int occ_fbcp(u32 block, size_t smem)
+// An H without an instantiation launches nothing.
+void launch_fb_h(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-	int nb = 0;
-	ensure_dyn_smem((const void *)fb_chain_post_kernel<H>, smem);
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)fb_chain_post_kernel<H>, (int)block, smem) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
-	return nb;
+	with_h(H, [&](auto h) { if (mega) launch_kernel(fb_kernel<MPC_H, true, false>, p, grid, block, smem, st); else launch_kernel(fb_kernel<MPC_H, false, false>, p, grid, block, smem, st); });
 }
-
-// does the instantiation keep values in scratch memory (the register allocator spilled)? The emulator has no registers to run out of.
-template <int H> bool fbcp_spills()
+void launch_fb_long(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-#ifdef MPC_EMU
-	return false;
-#else
-	hipFuncAttributes a;
-	if (hipFuncGetAttributes(&a, (const void *)fb_chain_post_kernel<H>) != hipSuccess) { (void)hipGetLastError(); return true; }
-	return a.localSizeBytes != 0;
-#endif
+	with_long_h(H, [&](auto h) { if (mega) launch_kernel(fb_kernel<MPC_H, true, true>, p, grid, block, smem, st); else launch_kernel(fb_kernel<MPC_H, false, true>, p, grid, block, smem, st); });
 }
-
-bool fbcp_spills_h(int H)
+void launch_fb_coop(int H, bool mega, const FbParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-	switch (H) {
-#define MPC_CASE(h) case h: return fbcp_spills<h>();
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: return true;
-	}
+	with_long_h(H, [&](auto h) { if (mega) launch_kernel(fb_coop_kernel<MPC_H, true>, p, grid, block, smem, st); else launch_kernel(fb_coop_kernel<MPC_H, false>, p, grid, block, smem, st); });
 }
-
-int occ_fbcp_h(int H, u32 block, size_t smem)
+void launch_fbc_h(int H, bool mega, const FbChainParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-	switch (H) {
-#define MPC_CASE(h) case h: return occ_fbcp<h>(block, smem);
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: return 0;
-	}
+	with_h(H, [&](auto h) { if (mega) launch_kernel(fb_chain_mega_kernel<MPC_H>, p, grid, block, smem, st); else launch_kernel(fb_chain_kernel<MPC_H>, p, grid, block, smem, st); });
 }
-
 void launch_fbcp_h(int H, const FbChainPostParams &p, u32 grid, u32 block, size_t smem, hipStream_t st)
 {
-	switch (H) {
-#define MPC_CASE(h) case h: launch_fbcp<h>(p, grid, block, smem, st); break;
-	MPC_CASE(1) MPC_CASE(2) MPC_CASE(3) MPC_CASE(4) MPC_CASE(5) MPC_CASE(6) MPC_CASE(7) MPC_CASE(8)
-	MPC_CASE(9) MPC_CASE(10) MPC_CASE(11) MPC_CASE(12) MPC_CASE(13) MPC_CASE(14) MPC_CASE(15) MPC_CASE(16)
-#undef MPC_CASE
-	default: break;
-	}
+	with_h(H, [&](auto h) { launch_kernel(fb_chain_post_kernel<MPC_H>, p, grid, block, smem, st); });
 }
+#undef MPC_H
 
 // shard buffer layout: [u64 npairs][u64 record_words_total][u32 nnz[np]][f32 ea[np]] pad to 8 | records
 u64 shard_header_bytes(u64 np) { return ((16 + np * 8 + 7) / 8) * 8; }
