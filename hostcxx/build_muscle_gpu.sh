@@ -15,7 +15,8 @@
 #                      - calcposteriorflat.o's CalcPosterior symbol, weakened with objcopy so that
 #                        hostcxx/mpcflat_gpu.cpp's strong definition wins while CalcPostFlat and the
 #                        two vestigial virtuals in the same object stay available; likewise one member each of
-#                        super7.o, uclust.o, pprog2.o, mpcflat.o (MPCFlat::CalcPosteriors) and swdistmx.o (CalcGuideTree_SW_BLOSUM62) - see below
+#                        super7.o, uclust.o, pprog2.o, mpcflat.o (MPCFlat::CalcPosteriors), swdistmx.o (CalcGuideTree_SW_BLOSUM62) and
+#                        eadistmx.o (CalcEADistMx) - see below
 #   + hostcxx/mpcflat_gpu.cpp (g++, against the reference headers) + hostcxx/rand_isolate.cpp
 #     (-Wl,--wrap=rand) + -lmpcgpu
 set -euo pipefail
@@ -69,7 +70,14 @@ objcopy --redefine-sym _ZN7MPCFlat16ProgressiveAlignEv=MPCFlat_ProgressiveAlign_
 SWSYM=_Z25CalcGuideTree_SW_BLOSUM62RK13MultiSequenceR4Tree
 read -r SWVAL SWSEC < <(objdump -t "$REFOBJ/swdistmx.o" | awk -v s="$SWSYM" '$NF == s && $2 == "g" { print $1, $4 }')
 objcopy --weaken-symbol="$SWSYM" --add-symbol "CalcGuideTree_SW_BLOSUM62_ref=$SWSEC:0x$SWVAL,global,function" "$REFOBJ/swdistmx.o" "$OUT/swdistmx_weak.o"
-OBJS=$(ls "$REFOBJ"/*.o | grep -v -e '/super7\.o$' -e '/uclust\.o$' -e '/alignpairflat\.o$' -e '/pprog2\.o$' -e '/mpcflat\.o$' -e '/progalnflat\.o$' -e '/swdistmx\.o$' | grep -v -e '/consflat\.o$' -e '/alnalnsflat\.o$' -e '/alnmsasflat\.o$' -e '/calcposteriorflat\.o$' -e '/buildpostflat\.o$' -e '/refineflat\.o$')
+# CalcEADistMx: ours (the EA of all pairs in one library call: `-eadistmx`, and the guide tree over the consensus sequences of -super4 /
+# -super5 through Super4::CalcConsensusSeqsDistMx). Handled like the function above: weakened in eadistmx.o, so cmd_eadistmx in the same
+# object — which stays the reference's — reaches our definition; the reference's loop stays reachable as CalcEADistMx_ref (a caller that
+# wants the sparse posteriors, and MUSCLE_GPU_EA_DISTMX=0).
+EASYM=$(objdump -t "$REFOBJ/eadistmx.o" | awk '$2 == "g" && $NF ~ /^_Z12CalcEADistMxP/ { print $NF }')
+read -r EAVAL EASEC < <(objdump -t "$REFOBJ/eadistmx.o" | awk -v s="$EASYM" '$NF == s && $2 == "g" { print $1, $4 }')
+objcopy --weaken-symbol="$EASYM" --add-symbol "CalcEADistMx_ref=$EASEC:0x$EAVAL,global,function" "$REFOBJ/eadistmx.o" "$OUT/eadistmx_weak.o"
+OBJS=$(ls "$REFOBJ"/*.o | grep -v -e '/super7\.o$' -e '/uclust\.o$' -e '/alignpairflat\.o$' -e '/pprog2\.o$' -e '/mpcflat\.o$' -e '/progalnflat\.o$' -e '/swdistmx\.o$' -e '/eadistmx\.o$' | grep -v -e '/consflat\.o$' -e '/alnalnsflat\.o$' -e '/alnmsasflat\.o$' -e '/calcposteriorflat\.o$' -e '/buildpostflat\.o$' -e '/refineflat\.o$')
 # The product links libmpcgpu.so. tests/test_dropin_emu.py re-runs this script with
 # MPCGPU_LIBDIR/MPCGPU_LIBNAME pointing at the SIMT-emulator build of the same library sources
 # (tests/emu, test infrastructure) to check the host-side plumbing of this file without a GPU.
@@ -78,7 +86,7 @@ LIBNAME="${MPCGPU_LIBNAME:-mpcgpu}"
 BIN="${MPCGPU_BIN:-muscle_gpu}"
 # --wrap=rand: the reference's rand() (refineflat.cpp:14) gets a private copy of glibc's default
 # stream; the HIP runtime in the same process otherwise consumes it (hostcxx/rand_isolate.cpp)
-g++ -O3 -fopenmp -pthread -Wl,--wrap=rand $OBJS "$OUT/calcposteriorflat_weak.o" "$OUT/super7_weak.o" "$OUT/uclust_weak.o" "$OUT/pprog2_weak.o" "$OUT/mpcflat_weak.o" "$OUT/progalnflat_weak.o" "$OUT/swdistmx_weak.o" "$OUT/mpcflat_gpu.o" "$OUT/rand_isolate.o" \
+g++ -O3 -fopenmp -pthread -Wl,--wrap=rand $OBJS "$OUT/calcposteriorflat_weak.o" "$OUT/super7_weak.o" "$OUT/uclust_weak.o" "$OUT/pprog2_weak.o" "$OUT/mpcflat_weak.o" "$OUT/progalnflat_weak.o" "$OUT/swdistmx_weak.o" "$OUT/eadistmx_weak.o" "$OUT/mpcflat_gpu.o" "$OUT/rand_isolate.o" \
   -L"$LIBDIR" -l"$LIBNAME" -Wl,-rpath,'$ORIGIN/../../muscle_amd/csrc' -Wl,-rpath,"$LIBDIR" -Wl,-rpath,/opt/rocm/lib -o "$OUT/$BIN"
 echo "built: $OUT/$BIN"
 # the product binary, beside the compiled reference (same depth below the root: the $ORIGIN run path holds from there too)

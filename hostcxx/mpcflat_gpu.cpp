@@ -373,7 +373,7 @@ bool DebugOn()
 
 // MUSCLE_GPU_TIMING=1: wall time spent inside the replaced functions, printed at exit (where does an
 // end-to-end run spend its time once the stage itself takes a few seconds).
-enum { T_STAGE_A, T_CONS_ITER, T_ALN_PREP, T_ALN_LIB, T_ALN_POST, T_JOIN_PREP, T_JOIN_LIB, T_PAIRS_PREP, T_PAIRS_LIB, T_SW_TREE, T_COUNT };
+enum { T_STAGE_A, T_CONS_ITER, T_ALN_PREP, T_ALN_LIB, T_ALN_POST, T_JOIN_PREP, T_JOIN_LIB, T_PAIRS_PREP, T_PAIRS_LIB, T_SW_TREE, T_EA_DISTMX, T_COUNT };
 // (atomics: the shrub and join workers of -super7 stop their watches concurrently — round-5 advisor finding)
 std::atomic<unsigned long long> g_Nanos[T_COUNT];
 std::atomic<unsigned long long> g_Calls[T_COUNT];
@@ -411,7 +411,7 @@ bool TimingOn()
 				{
 				static const char *Names[T_COUNT] = { "stage A (all pairs)", "ConsIter", "AlignAlns: maps",
 				  "AlignAlns: library", "AlignAlns: result MSA", "AlignMSAsFlat: pairs+maps", "AlignMSAsFlat: library",
-				  "AlignPairFlat lists: registry", "AlignPairFlat lists: library", "guide tree (SW)" };
+				  "AlignPairFlat lists: registry", "AlignPairFlat lists: library", "guide tree (SW)", "ea distmx" };
 				fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  (static initialisation to exit handlers; the rows below are parts of it)\n",
 				  "process", std::chrono::duration<double>(std::chrono::steady_clock::now() - g_ProcessStart).count());
 				fprintf(stderr, "[muscle_gpu] %-28s %10.3f s  (inside the first call below that needed it)\n", "context creation, HIP init", g_CtxSeconds);
@@ -2038,4 +2038,76 @@ void CalcGuideTree_SW_BLOSUM62(const MultiSequence &Input, Tree &T)
 	U.Init(Labels, DistMxv);
 	U.ScaleDistMx();
 	U.Run(LINKAGE_Avg, T);
+	}
+
+// ---------------------------------------------------------------------------------------------------------------
+// CalcEADistMx (eadistmx.cpp:7-70): the EA of every pair of a set — `muscle -eadistmx`, and through Super4::CalcConsensusSeqsDistMx
+// (super4.cpp:256-260) the guide tree over the cluster consensus sequences of every -super4 / -super5 run. The reference asks
+// AlignPairFlat for one pair per OpenMP thread and keeps one float of each answer; through the request combiner above that is a library
+// call per handful of pairs, each with its own tables, registry, trace-back and path copy. Here the floats of all pairs come from ONE
+// mpcgpu_ea_scores call on the calling thread's join context (no trace-back, no path: include/mpcgpu.h), the same bits, and everything
+// around them is the reference's: the matrix with its diagonal of 1 (eadistmx.cpp:10-17,63-64), the "%s\t%s\t%.4g" lines — in GetAllPairs
+// order, where the reference writes them in the order its threads finish — and one ProgressStep sequence with its format string (the
+// mean it shows is the running mean in pair order).
+// The sequences are the ones AlignPairFlat finds: by global label (calcpost.cpp:6-7,25-26), with the structure profiles of a .mega input.
+// A caller that wants the sparse posteriors (SparsePostVec != 0; none in the reference) keeps the reference's loop over
+// AlignPairFlat_SparsePost, as does MUSCLE_GPU_EA_DISTMX=0: CalcEADistMx_ref, the reference's function under a second name
+// (hostcxx/build_muscle_gpu.sh). UClust::Search, AlignPairFlat and EACluster are not touched: EACluster::GetBestCentroid's early exit
+// (eacluster.cpp) makes the reference's own answer depend on thread timing, so there is no list of pairs to take from it.
+extern "C" void CalcEADistMx_ref(FILE *f, MultiSequence *sequences, vector<vector<float> > &DistMx, vector<MySparseMx *> *SparsePostVec);
+void CalcEADistMx(FILE *f, MultiSequence *sequences, vector<vector<float> > &DistMx, vector<MySparseMx *> *SparsePostVec)
+	{
+	const char *Env = getenv("MUSCLE_GPU_EA_DISTMX");
+	const uint SeqCount = sequences->GetSeqCount();
+	if (SparsePostVec != 0 || (Env != 0 && *Env == '0') || SeqCount < 2)
+		{
+		CalcEADistMx_ref(f, sequences, DistMx, SparsePostVec);
+		return;
+		}
+// eadistmx.cpp:10-17
+	DistMx.clear();
+	DistMx.resize(SeqCount);
+	for (uint i = 0; i < SeqCount; ++i)
+		{
+		DistMx[i].resize(SeqCount, 0);
+		DistMx[i][i] = 1;
+		}
+	vector<string> Labels;
+	vector<const uint8_t *> Ptrs;
+	vector<uint32_t> Lens;
+	for (uint i = 0; i < SeqCount; ++i)
+		{
+		const string &Label = sequences->GetSequence(i)->m_Label;
+		const Sequence &Seq = GetGlobalInputSeqByLabel(Label);
+		Labels.push_back(Label);
+		Ptrs.push_back(Seq.GetBytePtr());
+		Lens.push_back(Seq.GetLength());
+		}
+	const uint64_t PairCount = uint64_t(SeqCount)*(SeqCount - 1)/2;
+	vector<float> EAs(PairCount);
+		{
+		Stopwatch SW(T_EA_DISTMX);
+		JoinCtx &J = JoinOfThisThread();
+		std::lock_guard<std::mutex> Guard(J.m_Mu);
+		mpcgpu_ctx *Ctx = J.m_Ctx;
+		GPUCHK(mpcgpu_set_hmm(Ctx, PairHMM::m_StartScore, &PairHMM::m_TransScore[0][0],
+		  &PairHMM::m_MatchScore[0][0], PairHMM::m_InsScore, MIN_SPARSE_SCORE, -1));
+		GPUCHK(mpcgpu_set_seqs_registry(Ctx, SeqCount, Ptrs.data(), Lens.data()));
+		SetMega(Ctx, Labels, Lens);
+		GPUCHK(mpcgpu_ea_scores(Ctx, PairCount, 0, 0, EAs.data()));
+		}
+	uint64_t PairIndex = 0;
+	float SumEA = 0;
+	for (uint i = 0; i < SeqCount; ++i)
+		for (uint j = i + 1; j < SeqCount; ++j)
+			{
+			double MeanEA = (PairIndex == 0 ? 0 : SumEA/PairIndex);
+			ProgressStep((uint) PairIndex, (uint) PairCount, "%u consensus seqs, mean EE %.2g", SeqCount, 1 - MeanEA);
+			const float EA = EAs[PairIndex++];
+			DistMx[i][j] = EA;
+			DistMx[j][i] = EA;
+			if (f != 0)
+				fprintf(f, "%s\t%s\t%.4g\n", Labels[i].c_str(), Labels[j].c_str(), EA);
+			SumEA += EA;
+			}
 	}

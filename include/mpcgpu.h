@@ -114,7 +114,9 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_chain_bins, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
  *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, mpcgpu_sw_set_scores, mpcgpu_sw_scores, mpcgpu_sw_info and mpcgpu_sw_bins (tables, letters,
  *   work lists and results of the local-alignment scores live in buffers of their own: shard, store, values and the stage-A scratch are
- *   neither read nor written), and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
+ *   neither read nor written), mpcgpu_ea_scores and mpcgpu_ea_info (the call runs stage A's sweeps in stage A's scratch, which holds nothing
+ *   between calls, and keeps its results in buffers of its own: shard, store, values and the results of the last stage A are neither read
+ *   nor written), and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
  * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
 int mpcgpu_store_epoch(mpcgpu_ctx *ctx, uint64_t *epoch);
@@ -361,6 +363,30 @@ int mpcgpu_sw_info(mpcgpu_ctx *ctx, uint64_t out[6]);
 /* last mpcgpu_sw_scores call, summed over its batches: per bin b = 1 .. MPC_SW_HMAX + 1 (index 0 unused; bins 1 .. 8: sw_kernel<b> with b
  * rows per lane, bin 9: the row-block kernel) items[b] = work items of the bin, groups[b] = workgroups launched for it (4 waves each) */
 int mpcgpu_sw_bins(mpcgpu_ctx *ctx, uint64_t items[10], uint64_t groups[10]);
+
+/* ---- EA of a list of pairs, nothing else: the distance matrix over consensus sequences (kernels_postea.h, mpcgpu_ea.inc) ----------------
+ * ea[q] = the float AlignPairFlat returns for (seq1[q], seq2[q]) — CalcAlnFlat's score over the dense thresholded posterior divided by
+ * min(L1, L2) (alignpairflat.cpp:11,19) — for pairs of the set given to mpcgpu_set_seqs_registry (or mpcgpu_set_seqs); seq1 == seq2 == NULL
+ * means all pairs i < j in InitPairs order (mpcflat.cpp:145-155; npairs must then be n (n - 1) / 2). Replaces the loop of CalcEADistMx
+ * (eadistmx.cpp:33-69), which keeps that one float per pair and throws the path away; the same bits as mpcgpu_calc_posteriors +
+ * mpcgpu_get_ea and as mpcgpu_align_pairs' ea.
+ * The forward/backward sweeps are stage A's own, through its dispatcher: chains where consecutive pairs share the row sequence,
+ * fb_kernel otherwise, row blocks from 769 rows on, structure profiles wherever mpcgpu_set_mega is in force. The finish is post_ea_kernel:
+ * probabilities and the EA recurrence exactly as post_rows_kernel forms them, one float out — no trace-back, no packed record, no sparse
+ * matrix; nothing is read back from the device but ea[]. The list runs in batches bounded like stage A's by MPCGPU_SCRATCH_GB (a pair costs
+ * its candidate room alone, so the batches are larger), and a batch whose candidate room overflows is redone with twice the room.
+ * A reader in the sense of mpcgpu_store_epoch: shard, store, committed values and what the getters and the info calls report of the last
+ * stage A stay as they are — mpcgpu_align_alns on a store built before the call gives what it gave before. (Stage A's scratch is used; no
+ * call keeps anything there.)
+ * Refused by name before any device work, the context left as it was: no sequences; one list NULL and the other not; a pair count that is
+ * not n (n - 1) / 2 with NULL lists; an index outside the set; a pair beyond the envelope of mpcgpu_align_pairs (LX * LY * 5 + 100 >
+ * INT_MAX, calcposteriorflat.cpp:54-61; more than 65 535 positions once the row sequence takes the row-block kernels); a list whose
+ * sequences do not fit the LDS arrays of the row-list finishing code (roughly LXmax + 2 * LYmax > 36 000: post_ea_kernel has no sort-based
+ * form — mpcgpu_align_pairs takes such pairs). */
+int mpcgpu_ea_scores(mpcgpu_ctx *ctx, uint64_t npairs, const uint32_t *seq1, const uint32_t *seq2, float *ea);
+/* The last mpcgpu_ea_scores call: out[0] pairs, out[1] batches, out[2] batches that were redone with a larger candidate room, out[3] launches
+ * of post_ea_kernel (batches + redone batches). All 0 before the first call; a refused call leaves them. */
+int mpcgpu_ea_info(mpcgpu_ctx *ctx, uint64_t out[4]);
 
 /* ---- several GPUs of one node inside ONE process (muscle_amd/csrc/mpcgpu_group.cpp) --------------------------
  * The drop-in binary is one process; it consumes the multi-GPU path through these calls. A group owns one context per

@@ -22,7 +22,7 @@ SYMBOLS = [
     "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_stage_a_chain_bins", "mpcgpu_stage_a_coop_info", "mpcgpu_stage_a_fuse_info", "mpcgpu_post_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
     "mpcgpu_work_get", "mpcgpu_synchronize", "mpcgpu_relax_info", "mpcgpu_shard_entries",
     "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch", "mpcgpu_store_epoch",
-    "mpcgpu_sw_set_scores", "mpcgpu_sw_scores", "mpcgpu_sw_info", "mpcgpu_sw_bins",
+    "mpcgpu_sw_set_scores", "mpcgpu_sw_scores", "mpcgpu_sw_info", "mpcgpu_sw_bins", "mpcgpu_ea_scores", "mpcgpu_ea_info",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
     "mpcgpu_group_transport", "mpcgpu_group_set_hmm", "mpcgpu_group_set_seqs", "mpcgpu_group_set_mega",
     "mpcgpu_group_calc_posteriors", "mpcgpu_group_cons_iter",
@@ -106,6 +106,8 @@ def load(lib_path=None):
     L.mpcgpu_sw_scores.argtypes = [vp, u64, vp, vp, vp]
     L.mpcgpu_sw_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_sw_bins.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.mpcgpu_ea_scores.argtypes = [vp, u64, vp, vp, vp]
+    L.mpcgpu_ea_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_relax_info.argtypes = [vp, C.c_char_p, u32, C.POINTER(i32)]
     L.mpcgpu_group_create.argtypes = [C.POINTER(vp), u32, vp]
     L.mpcgpu_group_destroy.argtypes = [vp]
@@ -565,6 +567,27 @@ class MpcGpu:
         items, groups = (C.c_uint64 * 10)(), (C.c_uint64 * 10)()
         self._ck(self.L.mpcgpu_sw_bins(self.h, items, groups))
         return tuple(int(x) for x in items), tuple(int(x) for x in groups)
+
+    def ea_scores(self, seq1=None, seq2=None):
+        """EA (AlignPairFlat's return value: alignment score over the thresholded posterior / min(L1, L2); no path, no matrix) of a list
+        of pairs of the registered sequences -> float32 array; no lists: all pairs i < j in InitPairs order"""
+        if seq1 is None and seq2 is None:
+            n = len(self.lens)
+            npairs = n * (n - 1) // 2
+            out = np.zeros(max(npairs, 1), np.float32)
+            self._ck(self.L.mpcgpu_ea_scores(self.h, npairs, None, None, out.ctypes.data))
+            return out[:npairs]
+        s1, s2 = np.ascontiguousarray(seq1, np.uint32), np.ascontiguousarray(seq2, np.uint32)
+        assert len(s1) == len(s2)
+        out = np.zeros(max(len(s1), 1), np.float32)
+        self._ck(self.L.mpcgpu_ea_scores(self.h, len(s1), s1.ctypes.data, s2.ctypes.data, out.ctypes.data))
+        return out[:len(s1)]
+
+    def ea_info(self):
+        """(pairs, batches, batches redone with a larger candidate room, launches of post_ea_kernel) of the last ea_scores call"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.L.mpcgpu_ea_info(self.h, out))
+        return tuple(int(x) for x in out)
 
     def build_post(self, seq1, seq2, p2c1, p2c2, C1, C2, w1=None, w2=None):
         """MPCFlat::BuildPost on the device store -> (C1, C2) float32 matrix (include/mpcgpu.h: mpcgpu_build_post)"""

@@ -258,18 +258,20 @@ template <bool WG> __device__ __forceinline__ void mpc_post_sync()
 
 // One pair by one wave (lane t): candidates cand[0 .. c) -> record, nnz, EA, flag. sorted: room for c entries (LDS or a slot in memory);
 // s_rend: LX + 1 words, s_cend and s_pm: LY + 1 words each, in LDS.
-template <bool WG>
+// FULL = false (post_ea_kernel, kernels_postea.h): the first half alone — probabilities, the row-sorted list, the EA recurrence — and
+// *ea_out the only thing written beside the two lists: rec, nnz_out and flags_out are not touched (the caller has tested c <= capc).
+template <bool WG, bool FULL = true>
 __device__ __forceinline__ void mpc_post_rows_pair(const int t, const u32 LX, const u32 LY, const u32 kshift, u64 *cand, const u32 c, const u32 capc,
 	u64 *sorted, u32 *rec, u32 *nnz_out, float *ea_out, u32 *flags_out, const int use_fma, const u32 batch, u32 *s_rend, u32 *s_cend, float *s_pm)
 {
-	if (c > capc) { // overflow: reported to the host, which retries with a larger capacity
+	if (FULL && c > capc) { // overflow: reported to the host, which retries with a larger capacity
 		if (t == 0) { *flags_out = 1u; *nnz_out = 0; *ea_out = 0.0f; }
 		return;
 	}
-	if (t == 0) *flags_out = 0u;
+	if (FULL && t == 0) *flags_out = 0u;
 	for (u32 q = t; q <= LX; q += 64) s_rend[q] = 0;
 	for (u32 q = t; q <= LY; q += 64) { s_cend[q] = 0; s_pm[q] = 0.0f; }
-	for (u32 q = t; q < LX + LY; q += 64) rec[q] = 0;
+	if (FULL) for (u32 q = t; q < LX + LY; q += 64) rec[q] = 0;
 	mpc_post_sync<WG>();
 	// ---- probabilities (calcposteriorflat.cpp:16-22) and the row histogram
 	for (u32 q = t; q < c; q += 64) {
@@ -410,6 +412,10 @@ __device__ __forceinline__ void mpc_post_rows_pair(const int t, const u32 LX, co
 	const float score = s_pm[LY < cmax ? LY : cmax];
 	const u32 mn = LX < LY ? LX : LY;
 	const float ea = score / (float)mn; // calcposteriorflat.cpp:89 (uint -> float, IEEE divide)
+	if (!FULL) {
+		if (t == 0) *ea_out = ea;
+		return;
+	}
 	mpc_post_sync<WG>();
 	// ---- sparsify (mysparsemx.cpp:115-152): keep P >= 0.01f, row-major rank among the kept
 	u32 kept = 0;

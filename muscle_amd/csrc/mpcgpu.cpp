@@ -1,5 +1,6 @@
 // mpcgpu.cpp — host side of libmpcgpu.so: the C ABI of include/mpcgpu.h over the HIP kernels in
 // kernels_fb.h (pair-HMM forward/backward, letter and structure-profile emissions), kernels_post.h (probabilities, sparsify, EA),
+// kernels_postea.h (probabilities and EA alone),
 // kernels_store.h (packed records, padded / slab stores, gather relax, commit, export),
 // kernels_relaxv.h (LDS-tiled relax over variable-size records), kernels_aln.h (posterior-DP alignment + traceback) and
 // kernels_prog.h (MSA x MSA posterior build). Built by hipcc (-x hip) for gfx950. There is no CPU
@@ -12,6 +13,7 @@
 #include "kernels_fbcoop.h"
 #include "kernels_post.h"
 #include "kernels_postw.h"
+#include "kernels_postea.h"
 #include "kernels_store.h"
 #include "kernels_relaxv.h"
 #include "kernels_relaxb.h"
@@ -282,6 +284,15 @@ struct mpcgpu_ctx {
 		u64 bin_items[MPC_SW_HMAX + 2] = {}, bin_groups[MPC_SW_HMAX + 2] = {}; // mpcgpu_sw_bins: per bin, summed over the batches
 		double ms = 0;
 	} sw;
+	// mpcgpu_ea_scores (mpcgpu_ea.inc): the result floats of a batch on the device and page-locked, the slots of post_ea_kernel's workgroups
+	// for lists beyond their LDS list, the event behind a batch's copy, the all-pairs list, and what mpcgpu_ea_info reports of the last call
+	struct EaState {
+		DevBuf d_ea, d_sort;
+		HostBuf h_ea;
+		hipEvent_t ev = nullptr;
+		std::vector<u32> v_x, v_y; // (kept: see v_flags above)
+		u64 pairs = 0, batches = 0, regrowths = 0, launches = 0;
+	} ea;
 };
 
 namespace {
@@ -738,6 +749,8 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->d_rects.release(); c->d_need.release(); c->d_exp_klist.release(); c->d_exp_valbase.release();
 	c->d_tiles2.release();
 	for (DevBuf *b : {&c->sw.d_let, &c->sw.d_off, &c->sw.d_tab, &c->sw.d_items, &c->sw.d_scores, &c->sw.d_queue, &c->sw.d_bnd}) b->release();
+	c->ea.d_ea.release(); c->ea.d_sort.release(); c->ea.h_ea.release();
+	if (c->ea.ev) (void)hipEventDestroy(c->ea.ev);
 	c->pad_seg.release(); release_windows(c);
 	if (c->ev_post) (void)hipEventDestroy(c->ev_post);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -1028,6 +1041,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *c) { return c ? c->npairs : 0; }
 #include "mpcgpu_exchange.inc"
 #include "mpcgpu_joins.inc"
 #include "mpcgpu_sw.inc"
+#include "mpcgpu_ea.inc"
 int mpcgpu_relax_info(mpcgpu_ctx *c, char *buf, uint32_t buflen, int *is_fallback)
 {
 	if (!c) return 1;

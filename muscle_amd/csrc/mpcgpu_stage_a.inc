@@ -248,10 +248,11 @@ static void build_chains(const mpcgpu_ctx *c, const ChainPlan &cp, u32 long_min,
 }
 
 // Batch [b0, b0 + B) of the list: B from the memory there is, the pairs binned by rows per lane and ordered by work.
-static int prepare_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &cp, u64 batch_budget, u64 np, const u32 *px, const u32 *py, u64 b0, BatchPrep &P)
+// records = false (mpcgpu_ea_scores): the batch leaves no fixed-stride records, a pair costs its candidate room alone.
+static int prepare_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &cp, u64 batch_budget, u64 np, const u32 *px, const u32 *py, u64 b0, BatchPrep &P, bool records = true)
 {
 	// ---- batch sizing: candidates + fixed-stride records per pair
-	const u64 per_pair = (u64)g.capc * 8 + g.res_stride() * 4 + 64;
+	const u64 per_pair = (u64)g.capc * 8 + (records ? g.res_stride() * 4 : 0) + 64;
 	size_t freeb = 0, totb = 0;
 	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
 	// the scratch of the previous batch (or of an overflow retry) is already owned and gets reused: count it as available
@@ -314,12 +315,12 @@ static int prepare_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &cp
 }
 
 // candidate lists, totals and fixed-stride records of B pairs; the work-queue heads (single pairs per bin, then chains per bin), zeroed
-static int ensure_pair_scratch(mpcgpu_ctx *c, const StageAGeom &g, u64 B)
+static int ensure_pair_scratch(mpcgpu_ctx *c, const StageAGeom &g, u64 B, bool records = true)
 {
 	HIPCHK(c, c->d_cand.ensure(B * g.capc * 8));
 	HIPCHK(c, c->d_cand_cnt.ensure(B * 4));
 	HIPCHK(c, c->d_total.ensure(B * 4));
-	HIPCHK(c, c->d_res.ensure(B * g.res_stride() * 4));
+	if (records) HIPCHK(c, c->d_res.ensure(B * g.res_stride() * 4));
 	HIPCHK(c, c->d_queue.ensure(4 * (2 * MPC_HMAX + 4)));
 	HIPCHK(c, hipMemsetAsync(c->d_queue.p, 0, 4 * (2 * MPC_HMAX + 4), c->stream));
 	return 0;
@@ -540,7 +541,8 @@ static int launch_fb_chains(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan 
 }
 
 // The sweeps of a batch: its index arrays go up (the NEXT set while the current batch is on the device), then row blocks, single pairs, chains.
-static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &plan, u64 planes_budget, BatchPrep &P, bool into_next)
+// records = false (mpcgpu_ea_scores; never with fused bins): no room for records, sizes, EA and flags — the sweeps leave candidate lists only.
+static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &plan, u64 planes_budget, BatchPrep &P, bool into_next, bool records = true)
 {
 	DevBuf &dbx = into_next ? c->d_bx_n : c->d_bx, &dby = into_next ? c->d_by_n : c->d_by, &dord = into_next ? c->d_order_n : c->d_order;
 	DevBuf &dcf = into_next ? c->d_chain_first_n : c->d_chain_first, &dcc = into_next ? c->d_chain_cnt_n : c->d_chain_cnt;
@@ -551,11 +553,13 @@ static int launch_fb_batch(mpcgpu_ctx *c, const StageAGeom &g, const ChainPlan &
 	if (upload(c, dbx, P.bx) || upload(c, dby, P.by) || upload(c, dord, P.order)) return 1;
 	if (!P.chain_first.empty() && (upload(c, dcf, P.chain_first) || upload(c, dcc, P.chain_cnt))) return 1;
 	if (plan.fuse_any && upload(c, into_next ? c->d_rest_n : c->d_rest, P.rest)) return 1;
-	if (ensure_pair_scratch(c, g, B)) return 1;
-	HIPCHK(c, dres.ensure(B * g.res_stride() * 4));
-	HIPCHK(c, dnnz.ensure(B * 4));
-	HIPCHK(c, dea.ensure(B * 4));
-	HIPCHK(c, dflags.ensure(B * 4));
+	if (ensure_pair_scratch(c, g, B, records)) return 1;
+	if (records) {
+		HIPCHK(c, dres.ensure(B * g.res_stride() * 4));
+		HIPCHK(c, dnnz.ensure(B * 4));
+		HIPCHK(c, dea.ensure(B * 4));
+		HIPCHK(c, dflags.ensure(B * 4));
+	}
 	FbChainPost post;
 	post.lx_cap = g.LXmax + 2; post.ly_cap = g.LYmax + 2; post.sort_cap = 0; post.wave_lds = 0;
 	post.batch = plan.post_batch; post.use_fma = c->use_fma;
