@@ -296,6 +296,10 @@ const std::chrono::steady_clock::time_point g_ProcessStart = std::chrono::steady
 // tables to build and no tiles to cut per store (MPCGPU_RELAX_SMALL_PAIRS, muscle_amd/csrc/mpcgpu.cpp: build_var_store; 4.6 ms of host
 // round trips per store otherwise, 412 stores in a 10 000-sequence run). Set here, before any thread exists; the user's own setting wins.
 const int g_SmallStoreDefault = setenv("MPCGPU_RELAX_SMALL_PAIRS", "40", 0);
+// CalcEADistMx below hands all pairs of consensus sequences to one mpcgpu_ea_scores call; a consensus sequence of 12 115 positions or more
+// is beyond the LDS arrays of its row-list finish, and the library refuses such a list unless the wide finish is switched on
+// (MPCGPU_EA_WIDE, muscle_amd/csrc/mpcgpu_ea.inc: post_wide_ea_kernel). Same place, same rule: the user's own setting wins.
+const int g_EaWideDefault = setenv("MPCGPU_EA_WIDE", "1", 0);
 // The allocator keeps freed memory mapped (blocks below 1 GB come from the heap, the heap's top is not trimmed). Host memory that the HIP
 // runtime has touched for a copy is registered for DMA; when glibc hands such a block back to the kernel (munmap above its moving mmap
 // threshold, or a trim), the kernel driver answers the invalidation by EVICTING the process's device queues and restoring them later:

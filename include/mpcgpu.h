@@ -375,18 +375,28 @@ int mpcgpu_sw_bins(mpcgpu_ctx *ctx, uint64_t items[10], uint64_t groups[10]);
  * probabilities and the EA recurrence exactly as post_rows_kernel forms them, one float out — no trace-back, no packed record, no sparse
  * matrix; nothing is read back from the device but ea[]. The list runs in batches bounded like stage A's by MPCGPU_SCRATCH_GB (a pair costs
  * its candidate room alone, so the batches are larger), and a batch whose candidate room overflows is redone with twice the room.
+ * post_ea_kernel keeps three per-position arrays in a CU's LDS, which two sequences of 12 115 positions no longer fit. With MPCGPU_EA_WIDE=1
+ * (unset = 0 in the library; the drop-in binary sets 1) the list is split: a pair whose longer sequence has at least MPCGPU_EA_WIDE_MIN
+ * positions (unset: 12 115 at the default MPCGPU_POST_SORT_CAP, the smallest length at which two such sequences stop fitting) is WIDE.
+ * The narrow pairs run as above, then the wide pairs the same way with post_wide_ea_kernel as the finish (kernels_postwea.h: a workgroup per
+ * pair, the first half of post_wide_kernel — radix sort, row starts in global scratch, the EA recurrence across all lanes; the same bits),
+ * each sub-list with its own geometry, batches and candidate room; the floats go back into the caller's order.
  * A reader in the sense of mpcgpu_store_epoch: shard, store, committed values and what the getters and the info calls report of the last
  * stage A stay as they are — mpcgpu_align_alns on a store built before the call gives what it gave before. (Stage A's scratch is used; no
  * call keeps anything there.)
  * Refused by name before any device work, the context left as it was: no sequences; one list NULL and the other not; a pair count that is
  * not n (n - 1) / 2 with NULL lists; an index outside the set; a pair beyond the envelope of mpcgpu_align_pairs (LX * LY * 5 + 100 >
  * INT_MAX, calcposteriorflat.cpp:54-61; more than 65 535 positions once the row sequence takes the row-block kernels); a list whose
- * sequences do not fit the LDS arrays of the row-list finishing code (roughly LXmax + 2 * LYmax > 36 000: post_ea_kernel has no sort-based
- * form — mpcgpu_align_pairs takes such pairs). */
+ * NARROW pairs do not fit the LDS arrays of the row-list finishing code (roughly LXmax + 2 * LYmax > 36 000) — without MPCGPU_EA_WIDE=1
+ * every pair is narrow (mpcgpu_align_pairs takes such pairs); with it, only under a MPCGPU_EA_WIDE_MIN above its default. */
 int mpcgpu_ea_scores(mpcgpu_ctx *ctx, uint64_t npairs, const uint32_t *seq1, const uint32_t *seq2, float *ea);
 /* The last mpcgpu_ea_scores call: out[0] pairs, out[1] batches, out[2] batches that were redone with a larger candidate room, out[3] launches
- * of post_ea_kernel (batches + redone batches). All 0 before the first call; a refused call leaves them. */
+ * of post_ea_kernel and post_wide_ea_kernel (batches + redone batches): totals over the narrow and the wide pairs. All 0 before the first
+ * call; a refused call leaves them. */
 int mpcgpu_ea_info(mpcgpu_ctx *ctx, uint64_t out[4]);
+/* ... and what of it went through post_wide_ea_kernel: out[0] wide pairs, out[1] their batches, out[2] those redone with a larger candidate
+ * room, out[3] launches of post_wide_ea_kernel. All 0 when no pair was wide. */
+int mpcgpu_ea_wide_info(mpcgpu_ctx *ctx, uint64_t out[4]);
 
 /* ---- several GPUs of one node inside ONE process (muscle_amd/csrc/mpcgpu_group.cpp) --------------------------
  * The drop-in binary is one process; it consumes the multi-GPU path through these calls. A group owns one context per

@@ -22,7 +22,7 @@ SYMBOLS = [
     "mpcgpu_get_sparse_range", "mpcgpu_post_scores", "mpcgpu_calc_aln", "mpcgpu_align_alns", "mpcgpu_align_alns_w", "mpcgpu_build_post", "mpcgpu_get_last_post", "mpcgpu_align_msas", "mpcgpu_align_pairs", "mpcgpu_get_list_sparse", "mpcgpu_stage_a_info", "mpcgpu_stage_a_chain_bins", "mpcgpu_stage_a_coop_info", "mpcgpu_stage_a_fuse_info", "mpcgpu_post_info", "mpcgpu_set_seqs_registry", "mpcgpu_timers_reset", "mpcgpu_timers_enable", "mpcgpu_timers_get",
     "mpcgpu_work_get", "mpcgpu_synchronize", "mpcgpu_relax_info", "mpcgpu_shard_entries",
     "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch", "mpcgpu_store_epoch",
-    "mpcgpu_sw_set_scores", "mpcgpu_sw_scores", "mpcgpu_sw_info", "mpcgpu_sw_bins", "mpcgpu_ea_scores", "mpcgpu_ea_info",
+    "mpcgpu_sw_set_scores", "mpcgpu_sw_scores", "mpcgpu_sw_info", "mpcgpu_sw_bins", "mpcgpu_ea_scores", "mpcgpu_ea_info", "mpcgpu_ea_wide_info",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
     "mpcgpu_group_transport", "mpcgpu_group_set_hmm", "mpcgpu_group_set_seqs", "mpcgpu_group_set_mega",
     "mpcgpu_group_calc_posteriors", "mpcgpu_group_cons_iter",
@@ -108,6 +108,7 @@ def load(lib_path=None):
     L.mpcgpu_sw_bins.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.mpcgpu_ea_scores.argtypes = [vp, u64, vp, vp, vp]
     L.mpcgpu_ea_info.argtypes = [vp, C.POINTER(u64)]
+    L.mpcgpu_ea_wide_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_relax_info.argtypes = [vp, C.c_char_p, u32, C.POINTER(i32)]
     L.mpcgpu_group_create.argtypes = [C.POINTER(vp), u32, vp]
     L.mpcgpu_group_destroy.argtypes = [vp]
@@ -584,9 +585,17 @@ class MpcGpu:
         return out[:len(s1)]
 
     def ea_info(self):
-        """(pairs, batches, batches redone with a larger candidate room, launches of post_ea_kernel) of the last ea_scores call"""
+        """(pairs, batches, batches redone with a larger candidate room, finishing launches) of the last ea_scores call: totals over
+        its narrow (post_ea_kernel) and wide (post_wide_ea_kernel) pairs"""
         out = (C.c_uint64 * 4)()
         self._ck(self.L.mpcgpu_ea_info(self.h, out))
+        return tuple(int(x) for x in out)
+
+    def ea_wide_info(self):
+        """(wide pairs, their batches, those redone with a larger candidate room, launches of post_wide_ea_kernel) of the last ea_scores
+        call (MPCGPU_EA_WIDE=1: pairs whose longer sequence has at least MPCGPU_EA_WIDE_MIN positions); all 0 when nothing went wide"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.L.mpcgpu_ea_wide_info(self.h, out))
         return tuple(int(x) for x in out)
 
     def build_post(self, seq1, seq2, p2c1, p2c2, C1, C2, w1=None, w2=None):

@@ -14,8 +14,8 @@
 // Working storage: the list itself (the score word of an entry becomes its probability, as in post_rows_kernel) and the row-sorted copy in
 // LDS or, for a list of more than sort_cap entries, in the workgroup's slot of sort_scratch.
 // Limit: the three per-position LDS arrays and the list must fit the CU's LDS, the test post_rows_kernel's host side makes
-// (post_rows_fits: roughly LXmax + 2 * LYmax <= 36 000); mpcgpu_ea_scores refuses a list beyond it by name — there is no sort-based or
-// workgroup-per-pair form of this kernel.
+// (post_rows_fits: roughly LXmax + 2 * LYmax <= 36 000). The pairs beyond it have a workgroup-per-pair form, post_wide_ea_kernel
+// (kernels_postwea.h): under MPCGPU_EA_WIDE=1 mpcgpu_ea_scores sends them there, without it the call refuses such a list by name.
 #pragma once
 #include "kernels_post.h"
 

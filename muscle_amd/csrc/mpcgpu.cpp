@@ -1,6 +1,6 @@
 // mpcgpu.cpp — host side of libmpcgpu.so: the C ABI of include/mpcgpu.h over the HIP kernels in
 // kernels_fb.h (pair-HMM forward/backward, letter and structure-profile emissions), kernels_post.h (probabilities, sparsify, EA),
-// kernels_postea.h (probabilities and EA alone),
+// kernels_postea.h, kernels_postwea.h (probabilities and EA alone: a wave / a workgroup per pair),
 // kernels_store.h (packed records, padded / slab stores, gather relax, commit, export),
 // kernels_relaxv.h (LDS-tiled relax over variable-size records), kernels_aln.h (posterior-DP alignment + traceback) and
 // kernels_prog.h (MSA x MSA posterior build). Built by hipcc (-x hip) for gfx950. There is no CPU
@@ -14,6 +14,7 @@
 #include "kernels_post.h"
 #include "kernels_postw.h"
 #include "kernels_postea.h"
+#include "kernels_postwea.h"
 #include "kernels_store.h"
 #include "kernels_relaxv.h"
 #include "kernels_relaxb.h"
@@ -285,13 +286,17 @@ struct mpcgpu_ctx {
 		double ms = 0;
 	} sw;
 	// mpcgpu_ea_scores (mpcgpu_ea.inc): the result floats of a batch on the device and page-locked, the slots of post_ea_kernel's workgroups
-	// for lists beyond their LDS list, the event behind a batch's copy, the all-pairs list, and what mpcgpu_ea_info reports of the last call
+	// for lists beyond their LDS list, the event behind a batch's copy, the all-pairs list, and what mpcgpu_ea_info reports of the last call;
+	// for the wide pairs (post_wide_ea_kernel) the slots of its workgroups — keys, row starts, DP rows, info words — and what
+	// mpcgpu_ea_wide_info reports
 	struct EaState {
 		DevBuf d_ea, d_sort;
+		DevBuf d_wkeys, d_wrs, d_wsrow, d_winfo;
 		HostBuf h_ea;
 		hipEvent_t ev = nullptr;
 		std::vector<u32> v_x, v_y; // (kept: see v_flags above)
 		u64 pairs = 0, batches = 0, regrowths = 0, launches = 0;
+		u64 wide_pairs = 0, wide_batches = 0, wide_regrowths = 0, wide_launches = 0;
 	} ea;
 };
 
@@ -750,6 +755,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->d_tiles2.release();
 	for (DevBuf *b : {&c->sw.d_let, &c->sw.d_off, &c->sw.d_tab, &c->sw.d_items, &c->sw.d_scores, &c->sw.d_queue, &c->sw.d_bnd}) b->release();
 	c->ea.d_ea.release(); c->ea.d_sort.release(); c->ea.h_ea.release();
+	c->ea.d_wkeys.release(); c->ea.d_wrs.release(); c->ea.d_wsrow.release(); c->ea.d_winfo.release();
 	if (c->ea.ev) (void)hipEventDestroy(c->ea.ev);
 	c->pad_seg.release(); release_windows(c);
 	if (c->ev_post) (void)hipEventDestroy(c->ev_post);

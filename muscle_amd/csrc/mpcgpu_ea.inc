@@ -1,4 +1,5 @@
-// mpcgpu_ea.inc — host side of post_ea_kernel (kernels_postea.h): mpcgpu_ea_scores, mpcgpu_ea_info. Included by mpcgpu.cpp inside its
+// mpcgpu_ea.inc — host side of post_ea_kernel (kernels_postea.h) and post_wide_ea_kernel (kernels_postwea.h): mpcgpu_ea_scores,
+// mpcgpu_ea_info, mpcgpu_ea_wide_info. Included by mpcgpu.cpp inside its
 // extern "C" block, behind mpcgpu_stage_a.inc, whose dispatcher it drives: the forward/backward sweeps are stage A's (chains, fb_kernel, row
 // blocks, structure profiles), batch by batch under the same MPCGPU_SCRATCH_GB, and only the finish differs — one float per pair, no
 // records, no pack, no shard. What the call uses of the context is stage A's SCRATCH (candidate lists, planes, index arrays: nothing a
@@ -40,6 +41,107 @@ int launch_post_ea(mpcgpu_ctx *c, const StageAGeom &g, u32 sort_cap, u32 batch, 
 	return span_end(c, &sp);
 }
 
+// post_wide_ea_kernel over the B pairs of the current batch: a workgroup of MPC_POSTW_THREADS per pair on a persistent grid, LDS and the
+// slots per workgroup sized as launch_post_wide sizes them (two key slots of capc entries for lists beyond the LDS buffers, LXmax + 1 row
+// starts, two DP rows of LYmax + 1 floats for pairs wider than the LDS rows, one info word), in buffers of mpcgpu_ctx::ea.
+// MPCGPU_POSTW_LDS (tests): as there.
+int launch_post_wide_ea(mpcgpu_ctx *c, const StageAGeom &g, u64 B)
+{
+	mpcgpu_ctx::EaState &e = c->ea;
+	const u32 T = MPC_POSTW_THREADS;
+	const int lds_env = env_int("MPCGPU_POSTW_LDS", -1);
+	PostWideEaParams pw;
+	pw.pair_x = c->d_bx.as<u32>(); pw.pair_y = c->d_by.as<u32>(); pw.seq_len = c->d_seq_len.as<u32>();
+	pw.cand = c->d_cand.as<u64>(); pw.capc = g.capc; pw.cand_cnt = c->d_cand_cnt.as<u32>();
+	pw.use_fma = c->use_fma;
+	pw.lds_cap = std::min<u32>(g.capc, lds_env >= 0 ? std::min<u32>((u32)lds_env, 4096u) : 4096u); // (launch_post_wide: 137 KB at the most, one workgroup per CU)
+	pw.srow_cap = std::min<u32>(g.LYmax + 1, lds_env >= 0 ? std::min<u32>((u32)lds_env, 4096u) : 4096u);
+	const size_t smem = mpc_postw_smem(T, pw.lds_cap, pw.srow_cap);
+	const int pocc = std::max(occ_blocks((const void *)post_wide_ea_kernel, T, smem), 1);
+	const u32 grid = (u32)std::max<u64>(std::min<u64>(B, (u64)c->prop.multiProcessorCount * (u32)pocc), 1);
+	pw.key_stride = g.capc; pw.rs_stride = (u64)g.LXmax + 1; pw.srow_stride = 2 * ((u64)g.LYmax + 1);
+	HIPCHK(c, e.d_wkeys.ensure(g.capc > pw.lds_cap ? (u64)grid * 2 * pw.key_stride * 8 : 8));
+	HIPCHK(c, e.d_wrs.ensure((u64)grid * pw.rs_stride * 4));
+	HIPCHK(c, e.d_wsrow.ensure(g.LYmax + 1 > pw.srow_cap ? (u64)grid * pw.srow_stride * 4 : 8));
+	HIPCHK(c, e.d_winfo.ensure((u64)grid * 8));
+	HIPCHK(c, e.d_ea.ensure(B * 4));
+	pw.key_scratch = e.d_wkeys.as<u64>(); pw.rs_scratch = e.d_wrs.as<u32>(); pw.srow_scratch = e.d_wsrow.as<float>();
+	pw.info = e.d_winfo.as<u64>();
+	pw.ea = e.d_ea.as<float>();
+	pw.count = (u32)B; pw.long_min = g.long_min;
+	if (trace_on()) { fprintf(stderr, "[mpcgpu] post wide ea: %llu pairs, %u threads per pair, lists of %u candidates and rows of %u floats in LDS, lds=%zu B grid=%u\n", (unsigned long long)B, T, pw.lds_cap, pw.srow_cap, smem, grid); fflush(stderr); }
+	TimedSpan sp;
+	if (span_begin(c, 1, &sp)) return 1;
+	MPC_LAUNCH(post_wide_ea_kernel, grid, T, smem, c->stream, pw);
+	HIPCHK(c, hipGetLastError());
+	e.launches += 1; e.wide_launches += 1;
+	return span_end(c, &sp);
+}
+
+// MPCGPU_EA_WIDE_MIN unset: the smallest m for which two sequences of m positions no longer fit the row-list arrays (12 115 at the default
+// sort cap of 1024). post_rows_fits is monotone in both lengths, so the pairs whose longer sequence stays below m fit together whatever
+// mix of row and column lengths their list holds.
+u32 ea_wide_min_default(u32 sort_cap)
+{
+	u32 m = 1;
+	const size_t fixed = 32 + 8 * (size_t)sort_cap; // post_rows_fits: (3 m + 6) * 4 + 8 + 8 * sort_cap <= 150 KB
+	if (fixed < 150 * 1024) m = (u32)((150 * 1024 - fixed) / 12) + 1;
+	while (m > 1 && !post_rows_fits(m - 1, m - 1, sort_cap)) --m;
+	while (post_rows_fits(m, m, sort_cap)) ++m;
+	return m;
+}
+
+// One sub-list of mpcgpu_ea_scores (n > 0 pairs px[], py[]; g = stage_a_geom of the sub-list) through stage A's sweeps and its finishing
+// kernel — post_ea_kernel, or post_wide_ea_kernel for the wide pairs. Float q of the sub-list goes to ea[where[q]] (where == NULL: ea[q]).
+int ea_sublist(mpcgpu_ctx *c, StageAGeom g, u64 n, const u32 *px, const u32 *py, u32 sort_cap, bool wide, const u64 *where, float *ea)
+{
+	mpcgpu_ctx::EaState &e = c->ea;
+	const ScratchBudget budget = scratch_budget();
+	ChainPlan chain; // (no fuse_plan: a fused bin would write records)
+	if (chain_plan(c, g, budget.planes, chain)) return 1;
+	const u32 post_batch = (u32)std::max(env_int("MPCGPU_POST_BATCH", 64), 1);
+	// The batches as stage A queues them, without records and pack: fb(0) ea(0) copy(0) | fb(1) ea(1) copy(1) | ... on one stream; the host
+	// prepares batch b + 1 and queues its sweeps before it waits for the floats of batch b (an event behind the copy).
+	BatchPrep cur, nxt;
+	u64 done = 0;
+	if (prepare_batch(c, g, chain, budget.batch, n, px, py, 0, cur, false) || launch_fb_batch(c, g, chain, budget.planes, cur, false, false)) return 1;
+	while (done < n) {
+		const u64 B = cur.B;
+		if (wide ? launch_post_wide_ea(c, g, B) : launch_post_ea(c, g, sort_cap, post_batch, B)) return 1;
+		HIPCHK(c, e.h_ea.ensure(B * 4));
+		HIPCHK(c, hipMemcpyAsync(e.h_ea.p, e.d_ea.p, B * 4, hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipEventRecord(e.ev, c->stream));
+		nxt.valid = false;
+		if (done + B < n && (prepare_batch(c, g, chain, budget.batch, n, px, py, done + B, nxt, false) || launch_fb_batch(c, g, chain, budget.planes, nxt, true, false))) return 1;
+		HIPCHK(c, hipEventSynchronize(e.ev));
+		const float *got = e.h_ea.as<float>();
+		bool overflow = false;
+		for (u64 q = 0; q < B; ++q) overflow = overflow || got[q] < 0.0f; // MPC_EA_OVERFLOW
+		if (overflow) {
+			const u64 room = (u64)g.LXmax * g.LYmax;
+			if (g.capc >= room) return fail(c, "mpcgpu_ea_scores: candidate overflow at full capacity (internal error)");
+			if (trace_on()) { fprintf(stderr, "[mpcgpu] ea overflow: batch at pair %llu (%llu pairs) redone, capc %u -> %llu\n", (unsigned long long)done, (unsigned long long)B, g.capc, (unsigned long long)std::min<u64>((u64)g.capc * 2, room)); fflush(stderr); }
+			g.capc = (u32)std::min<u64>((u64)g.capc * 2, room);
+			e.regrowths += 1; e.wide_regrowths += wide ? 1 : 0;
+			// this batch again with a larger candidate room: the next batch's sweeps, queued behind it, are drained and dropped
+			HIPCHK(c, hipStreamSynchronize(c->stream));
+			if (prepare_batch(c, g, chain, budget.batch, n, px, py, done, cur, false) || launch_fb_batch(c, g, chain, budget.planes, cur, false, false)) return 1;
+			continue;
+		}
+		if (where) for (u64 q = 0; q < B; ++q) ea[where[done + q]] = got[q];
+		else memcpy(ea + done, got, B * 4);
+		done += B;
+		e.batches += 1; e.wide_batches += wide ? 1 : 0;
+		std::swap(cur, nxt);
+		if (cur.valid) { // the next batch's index arrays become the current set
+			std::swap(c->d_bx, c->d_bx_n); std::swap(c->d_by, c->d_by_n); std::swap(c->d_order, c->d_order_n);
+			std::swap(c->d_chain_first, c->d_chain_first_n); std::swap(c->d_chain_cnt, c->d_chain_cnt_n);
+		}
+	}
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	return 0;
+}
+
 } // namespace
 } // extern "C++"
 
@@ -76,58 +178,41 @@ int mpcgpu_ea_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const
 	if (g.LXlong > MPC_KEY_COL_MASK_LONG || g.LYlong > MPC_KEY_COL_MASK_LONG)
 		return fail(c, "mpcgpu_ea_scores: a pair of %u x %u positions is beyond this build's limit of %u per sequence once the row sequence is longer than %u",
 			g.LXlong, g.LYlong, MPC_KEY_COL_MASK_LONG, g.long_min - 1);
-	// ... and the LDS arrays of the row-list finishing code (post_ea_kernel has no other form: kernels_postea.h)
+	// ... and the LDS arrays of the row-list finishing code, which the NARROW pairs of the list share. MPCGPU_EA_WIDE=1 (unset = 0 in the library;
+	// the drop-in binary sets 1): a pair whose longer sequence has at least MPCGPU_EA_WIDE_MIN positions is WIDE and finishes in
+	// post_wide_ea_kernel, which has no such arrays; without it every pair is narrow and a list beyond the arrays is refused.
 	const u32 sort_cap = (u32)std::max(env_int("MPCGPU_POST_SORT_CAP", 1024), 2);
-	if (!post_rows_fits(g.LXmax, g.LYmax, sort_cap))
+	const bool wide_on = env_int("MPCGPU_EA_WIDE", 0) == 1;
+	const u32 wide_min = wide_on ? (u32)std::max(env_int("MPCGPU_EA_WIDE_MIN", (int)ea_wide_min_default(sort_cap)), 1) : 0;
+	u64 nwide = 0;
+	if (wide_on)
+		for (u64 q = 0; q < npairs; ++q) nwide += std::max(c->len[px[q]], c->len[py[q]]) >= wide_min ? 1 : 0;
+	std::vector<u32> sx, sy; // the narrow pairs, then the wide ones, each in list order; sq: where in the caller's list
+	std::vector<u64> sq;
+	if (nwide != 0 && nwide != npairs) {
+		sx.resize(npairs); sy.resize(npairs); sq.resize(npairs);
+		u64 kn = 0, kw = npairs - nwide;
+		for (u64 q = 0; q < npairs; ++q) {
+			u64 &k = std::max(c->len[px[q]], c->len[py[q]]) >= wide_min ? kw : kn;
+			sx[k] = px[q]; sy[k] = py[q]; sq[k] = q; ++k;
+		}
+		px = sx.data(); py = sy.data();
+	}
+	const u64 nnarrow = npairs - nwide;
+	StageAGeom gn = g, gw = g; // (one sub-list: the geometry of the list)
+	if (!sq.empty()) { gn = stage_a_geom(c, nnarrow, px, py); gw = stage_a_geom(c, nwide, px + nnarrow, py + nnarrow); }
+	if (nnarrow && !post_rows_fits(gn.LXmax, gn.LYmax, sort_cap))
 		return fail(c, "mpcgpu_ea_scores: sequences of %u and %u positions do not fit the LDS arrays of post_ea_kernel (roughly LXmax + 2 * LYmax <= 36 000; "
-			"mpcgpu_align_pairs takes such pairs)", g.LXmax, g.LYmax);
+			"mpcgpu_align_pairs takes such pairs)", gn.LXmax, gn.LYmax);
 	e.pairs = npairs; e.batches = e.regrowths = e.launches = 0;
+	e.wide_pairs = nwide; e.wide_batches = e.wide_regrowths = e.wide_launches = 0;
 	if (npairs == 0) return 0;
 
 	HIPCHK(c, hipSetDevice(c->device));
-	const ScratchBudget budget = scratch_budget();
-	ChainPlan chain; // (no fuse_plan: a fused bin would write records)
-	if (chain_plan(c, g, budget.planes, chain)) return 1;
-	const u32 post_batch = (u32)std::max(env_int("MPCGPU_POST_BATCH", 64), 1);
 	if (!e.ev) HIPCHK(c, hipEventCreateWithFlags(&e.ev, hipEventDisableTiming));
-	// The batches as stage A queues them, without records and pack: fb(0) ea(0) copy(0) | fb(1) ea(1) copy(1) | ... on one stream; the host
-	// prepares batch b + 1 and queues its sweeps before it waits for the floats of batch b (an event behind the copy).
-	BatchPrep cur, nxt;
-	u64 done = 0;
-	if (prepare_batch(c, g, chain, budget.batch, npairs, px, py, 0, cur, false) || launch_fb_batch(c, g, chain, budget.planes, cur, false, false)) return 1;
-	while (done < npairs) {
-		const u64 B = cur.B;
-		if (launch_post_ea(c, g, sort_cap, post_batch, B)) return 1;
-		HIPCHK(c, e.h_ea.ensure(B * 4));
-		HIPCHK(c, hipMemcpyAsync(e.h_ea.p, e.d_ea.p, B * 4, hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipEventRecord(e.ev, c->stream));
-		nxt.valid = false;
-		if (done + B < npairs && (prepare_batch(c, g, chain, budget.batch, npairs, px, py, done + B, nxt, false) || launch_fb_batch(c, g, chain, budget.planes, nxt, true, false))) return 1;
-		HIPCHK(c, hipEventSynchronize(e.ev));
-		const float *got = e.h_ea.as<float>();
-		bool overflow = false;
-		for (u64 q = 0; q < B; ++q) overflow = overflow || got[q] < 0.0f; // MPC_EA_OVERFLOW
-		if (overflow) {
-			const u64 room = (u64)g.LXmax * g.LYmax;
-			if (g.capc >= room) return fail(c, "mpcgpu_ea_scores: candidate overflow at full capacity (internal error)");
-			if (trace_on()) { fprintf(stderr, "[mpcgpu] ea overflow: batch at pair %llu (%llu pairs) redone, capc %u -> %llu\n", (unsigned long long)done, (unsigned long long)B, g.capc, (unsigned long long)std::min<u64>((u64)g.capc * 2, room)); fflush(stderr); }
-			g.capc = (u32)std::min<u64>((u64)g.capc * 2, room);
-			e.regrowths += 1;
-			// this batch again with a larger candidate room: the next batch's sweeps, queued behind it, are drained and dropped
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			if (prepare_batch(c, g, chain, budget.batch, npairs, px, py, done, cur, false) || launch_fb_batch(c, g, chain, budget.planes, cur, false, false)) return 1;
-			continue;
-		}
-		memcpy(ea + done, got, B * 4);
-		done += B;
-		e.batches += 1;
-		std::swap(cur, nxt);
-		if (cur.valid) { // the next batch's index arrays become the current set
-			std::swap(c->d_bx, c->d_bx_n); std::swap(c->d_by, c->d_by_n); std::swap(c->d_order, c->d_order_n);
-			std::swap(c->d_chain_first, c->d_chain_first_n); std::swap(c->d_chain_cnt, c->d_chain_cnt_n);
-		}
-	}
-	HIPCHK(c, hipStreamSynchronize(c->stream));
+	const u64 *where = sq.empty() ? nullptr : sq.data();
+	if (nnarrow && ea_sublist(c, gn, nnarrow, px, py, sort_cap, false, where, ea)) return 1;
+	if (nwide && ea_sublist(c, gw, nwide, px + nnarrow, py + nnarrow, sort_cap, true, where ? where + nnarrow : nullptr, ea)) return 1;
 	return 0;
 }
 
@@ -137,5 +222,14 @@ int mpcgpu_ea_info(mpcgpu_ctx *c, uint64_t out[4])
 	if (!out) return fail(c, "mpcgpu_ea_info: NULL argument");
 	const mpcgpu_ctx::EaState &e = c->ea;
 	out[0] = e.pairs; out[1] = e.batches; out[2] = e.regrowths; out[3] = e.launches;
+	return 0;
+}
+
+int mpcgpu_ea_wide_info(mpcgpu_ctx *c, uint64_t out[4])
+{
+	if (!c) return 1;
+	if (!out) return fail(c, "mpcgpu_ea_wide_info: NULL argument");
+	const mpcgpu_ctx::EaState &e = c->ea;
+	out[0] = e.wide_pairs; out[1] = e.wide_batches; out[2] = e.wide_regrowths; out[3] = e.wide_launches;
 	return 0;
 }
