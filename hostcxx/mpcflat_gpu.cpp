@@ -383,6 +383,7 @@ std::atomic<unsigned long long> g_Nanos[T_COUNT];
 std::atomic<unsigned long long> g_Calls[T_COUNT];
 std::atomic<unsigned long long> g_SwKernelNanos; // device time of sw_kernel inside the "guide tree (SW)" row (mpcgpu_sw_info)
 std::atomic<unsigned long long> g_SwCells;
+std::atomic<unsigned long long> g_UpgmaPrepNanos, g_UpgmaJoinNanos; // MUSCLE_GPU_UPGMA=1: device time of transform + initialisation and of the join loop (mpcgpu_upgma_info)
 // The timeline of ONE MPCFlat::Run (muscle -align): when the replaced functions were entered first / left last, in ns since process
 // start. What lies BETWEEN them is the reference's own host code — the row f4 of SURVEY.md 8 (CalcGuideTree = UPGMA5,
 // upgma5.cpp:87-..., ClustalWeights, CalcJoinOrder, the bookkeeping of ProgAln / RefineIter, SortMSA, output) — which this file does
@@ -424,6 +425,9 @@ bool TimingOn()
 				if (g_Calls[T_SW_TREE].load() != 0)
 					fprintf(stderr, "[muscle_gpu]   guide tree (SW): kernel %.3f s for %llu DP cells; the rest of the row is the letters' upload, the distance matrix and UPGMA5\n",
 					  g_SwKernelNanos.load()*1e-9, g_SwCells.load());
+				if (g_UpgmaJoinNanos.load() != 0)
+					fprintf(stderr, "[muscle_gpu]   guide tree (SW): on the device also normalisation, scaling and row minima %.3f s, UPGMA5 join loop %.3f s\n",
+					  g_UpgmaPrepNanos.load()*1e-9, g_UpgmaJoinNanos.load()*1e-9);
 				fprintf(stderr, "[muscle_gpu] posterior stage: computed %llu reused %llu\n", g_StagesComputed.load(), g_StagesReused.load());
 // (one MPCFlat::Run only: with the shrub workers of -super7 running many at once first-entered / last-left marks interleave)
 				const bool OneRun = g_Mark[M_POST_ENTER].load() != 0 && g_Mark[M_POST_ENTER].load() <= g_Mark[M_POST_EXIT].load() &&
@@ -1984,6 +1988,7 @@ void Super7::IntraAlignShrubs()
 // Besti + 1 passed in, so the reference aborts whenever a pair's best local alignment ends on the last residue of either sequence;
 // the scores are complete before that point, and the tree built here is the tree those scores define.
 // MUSCLE_GPU_SW_TREE=0: the reference's own loop, kept in the binary as CalcGuideTree_SW_BLOSUM62_ref (hostcxx/build_muscle_gpu.sh).
+// MUSCLE_GPU_UPGMA=1: the whole function in one library call (mpcgpu_sw_tree), see below; off unless asked for.
 extern float Blosum62_sij[20][20]; // blosum.cpp:8
 extern "C" void CalcGuideTree_SW_BLOSUM62_ref(const MultiSequence &Input, Tree &T);
 void CalcGuideTree_SW_BLOSUM62(const MultiSequence &Input, Tree &T)
@@ -2007,7 +2012,17 @@ void CalcGuideTree_SW_BLOSUM62(const MultiSequence &Input, Tree &T)
 		Lens.push_back(Seq.GetLength());
 		}
 	const uint64_t PairCount = uint64_t(SeqCount)*(SeqCount - 1)/2;
-	vector<float> Scores(PairCount);
+// MUSCLE_GPU_UPGMA=1: normalisation, ScaleDistMx and UPGMA5::Run on the device as well (mpcgpu_sw_tree: kernels_upgma.h restates them bit
+// for bit). No score and no n x n matrix reaches the host: the four arrays UPGMA5::Run hands to Tree::Create come back (upgma5.cpp:306-309),
+// and Min / Max for ScaleDistMx's two log lines (upgma5.cpp:536, 561; the scaled extremes are the transform of Max and of Min: it is
+// monotone). Unset or 0: the scores come back and the host's UPGMA5 clusters them, as below. Beyond 65 536 sequences, where the
+// reference's triangle subscript wraps, the host route is taken as before.
+	const char *EnvU = getenv("MUSCLE_GPU_UPGMA");
+	const bool DeviceTree = (EnvU != 0 && *EnvU != 0 && *EnvU != '0') && SeqCount <= 65536;
+	vector<float> Scores(DeviceTree ? 0 : PairCount);
+	vector<uint> Left, Right;
+	vector<float> LeftLength, RightLength;
+	float MinMax[2] = { 0, 0 };
 		{
 // a context of its own, gone before the shrubs start: the scores need nothing of the posterior stage's state. mpcgpu_set_seqs_registry
 // wants pair-HMM tables first; none of them enters a score (InitProbcons has not run yet, super7.cpp:170).
@@ -2018,12 +2033,46 @@ void CalcGuideTree_SW_BLOSUM62(const MultiSequence &Input, Tree &T)
 		  PairHMM::m_InsScore, MIN_SPARSE_SCORE, -1));
 		GPUCHK(mpcgpu_set_seqs_registry(Ctx, SeqCount, Ptrs.data(), Lens.data()));
 		GPUCHK(mpcgpu_sw_set_scores(Ctx, g_CharToLetterAmino, 20, &Blosum62_sij[0][0], -11, -1)); // swdistmx.cpp:106-107
-		GPUCHK(mpcgpu_sw_scores(Ctx, PairCount, 0, 0, Scores.data()));
+		if (DeviceTree)
+			{
+			Left.resize(SeqCount - 1);
+			Right.resize(SeqCount - 1);
+			LeftLength.resize(SeqCount - 1);
+			RightLength.resize(SeqCount - 1);
+			GPUCHK(mpcgpu_sw_tree(Ctx, MPCGPU_UPGMA_AVG, Left.data(), Right.data(), LeftLength.data(), RightLength.data(), 0));
+			GPUCHK(mpcgpu_upgma_scale(Ctx, MinMax));
+			uint64_t UInfo[4];
+			GPUCHK(mpcgpu_upgma_info(Ctx, UInfo));
+			g_UpgmaPrepNanos += UInfo[2];
+			g_UpgmaJoinNanos += UInfo[3];
+			}
+		else
+			GPUCHK(mpcgpu_sw_scores(Ctx, PairCount, 0, 0, Scores.data()));
 		uint64_t Info[6];
 		GPUCHK(mpcgpu_sw_info(Ctx, Info));
 		g_SwKernelNanos += Info[5];
 		g_SwCells += Info[1];
 		mpcgpu_destroy(Ctx);
+		}
+	if (DeviceTree)
+		{
+		const float SCALE = 10.0f; // upgma5.cpp:523
+		ProgressLog("Re-scaling, min %.4g, max %.4g\n", MinMax[0], MinMax[1]); // upgma5.cpp:536
+		const float MinNewDist = SCALE*(MinMax[1] - MinMax[1])/(MinMax[1] - MinMax[0]);
+		const float MaxNewDist = SCALE*(MinMax[1] - MinMax[0])/(MinMax[1] - MinMax[0]);
+		ProgressLog("Scaled min dist %.3g, max %.3g. scale\n", MinNewDist, MaxNewDist, SCALE); // upgma5.cpp:561
+		ProgressStep(0, SeqCount - 1, "UPGMA5"); // upgma5.cpp:170
+		if (SeqCount > 2)
+			ProgressStep(SeqCount - 2, SeqCount - 1, "UPGMA5");
+		vector<uint> Ids(SeqCount);
+		vector<char *> Names(SeqCount);
+		for (uint i = 0; i < SeqCount; ++i)
+			{
+			Ids[i] = i;
+			Names[i] = const_cast<char *>(Labels[i].c_str()); // Tree::Create copies them (tree.cpp:1466)
+			}
+		T.Create(SeqCount, SeqCount - 2, Left.data(), Right.data(), LeftLength.data(), RightLength.data(), Ids.data(), Names.data()); // upgma5.cpp:307-309
+		return;
 		}
 	vector<vector<float> > DistMxv(SeqCount);
 	for (uint i = 0; i < SeqCount; ++i)

@@ -116,7 +116,8 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   work lists and results of the local-alignment scores live in buffers of their own: shard, store, values and the stage-A scratch are
  *   neither read nor written), mpcgpu_ea_scores and mpcgpu_ea_info (the call runs stage A's sweeps in stage A's scratch, which holds nothing
  *   between calls, and keeps its results in buffers of its own: shard, store, values and the results of the last stage A are neither read
- *   nor written), and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
+ *   nor written), mpcgpu_upgma, mpcgpu_sw_tree, mpcgpu_upgma_info and mpcgpu_upgma_scale (triangle, row state and tree arrays live in
+ *   buffers of their own; mpcgpu_sw_tree's scores in those of mpcgpu_sw_scores), and mpcgpu_group_create, _destroy, _last_error, _size, _ctx, _transport.
  * (mpcgpu_values_info hands out the device address of the NEXT values, which the caller of a sharded run writes itself: such a
  * write is seen by no reader until mpcgpu_cons_commit(_range), which moves the epoch.) */
 int mpcgpu_store_epoch(mpcgpu_ctx *ctx, uint64_t *epoch);
@@ -363,6 +364,44 @@ int mpcgpu_sw_info(mpcgpu_ctx *ctx, uint64_t out[6]);
 /* last mpcgpu_sw_scores call, summed over its batches: per bin b = 1 .. MPC_SW_HMAX + 1 (index 0 unused; bins 1 .. 8: sw_kernel<b> with b
  * rows per lane, bin 9: the row-block kernel) items[b] = work items of the bin, groups[b] = workgroups launched for it (4 waves each) */
 int mpcgpu_sw_bins(mpcgpu_ctx *ctx, uint64_t items[10], uint64_t groups[10]);
+
+/* ---- UPGMA on the device (kernels_upgma.h, mpcgpu_upgma.inc) ----------------------------------------------------------------
+ * The tree UPGMA5 builds from a distance matrix. dist: the n (n - 1) / 2 distances of the pairs i < j in InitPairs order
+ * (mpcflat.cpp:145-155), the order mpcgpu_sw_scores and mpcgpu_ea_scores write. transform, applied first:
+ *   MPCGPU_UPGMA_NONE        the values as they are (cmd_upgma5 without options, upgma5.cpp:578)
+ *   MPCGPU_UPGMA_SCALE_SIM   UPGMA5::ScaleDistMx(true), upgma5.cpp:521-563: 10 * (Max - d) / (Max - Min) (-scaledist, -reseek, swdistmx.cpp:125)
+ *   MPCGPU_UPGMA_SCALE_DIST  UPGMA5::ScaleDistMx(false): 10 * (d - Min) / (Max - Min)
+ *   MPCGPU_UPGMA_EA          UPGMA5::FixEADistMx, upgma5.cpp:504-519: 1 - d (-eadist)
+ * Then UPGMA5::Run(linkage), upgma5.cpp:87-305: negative distances become 0, every row's smallest distance and nearest neighbour, and n - 1
+ * joins with the linkage formula MPCGPU_UPGMA_AVG, _MIN, _MAX or _BIASED (upgma5.cpp:227-247) — the reference's procedure statement by
+ * statement, with the cached row minima it never repairs and the neighbour redirect of upgma5.cpp:249-259, every float rounded as the
+ * reference rounds it. Outputs, n - 1 entries each: the arrays UPGMA5::Run hands to Tree::Create (upgma5.cpp:306-308) — left / right child
+ * of internal node k (a value < n is a leaf, n + k' internal node k'), and the branch lengths to them. The root is node n - 2.
+ * One persistent workgroup runs the joins; the per-row state is in LDS up to MPCGPU_UPGMA_LDS_ROWS rows (12 288, also the most), in global
+ * memory beyond. Only the triangle goes to the device and 4 (n - 1) words come back.
+ * Refused by name before any device work, the context left as it was: n < 2; n > 65 536 (upgma5.h:68: the reference's own 32-bit
+ * uIndex1 * (uIndex1 - 1) wraps there); an unknown transform or linkage; a NULL argument; a triangle that does not fit the device's free
+ * memory. Refused by name after the run, the outputs untouched: an EA value outside 0 .. 1 (the reference dies, upgma5.cpp:512); a join
+ * that finds no distance below FLT_MAX (the reference asserts, upgma5.cpp:197-199: all remaining distances FLT_MAX or NaN, as after
+ * scaling a matrix whose entries are all equal).
+ * A reader in the sense of mpcgpu_store_epoch, with buffers of its own. */
+enum { MPCGPU_UPGMA_NONE = 0, MPCGPU_UPGMA_SCALE_SIM = 1, MPCGPU_UPGMA_SCALE_DIST = 2, MPCGPU_UPGMA_EA = 3 };
+enum { MPCGPU_UPGMA_AVG = 0, MPCGPU_UPGMA_MIN = 1, MPCGPU_UPGMA_MAX = 2, MPCGPU_UPGMA_BIASED = 3 };
+int mpcgpu_upgma(mpcgpu_ctx *ctx, uint32_t n, const float *dist, int transform, int linkage, uint32_t *left, uint32_t *right,
+                 float *left_len, float *right_len);
+/* The guide tree of CalcGuideTree_SW_BLOSUM62 (swdistmx.cpp:87-127) for the set given to mpcgpu_set_seqs(_registry), with the tables of
+ * mpcgpu_sw_set_scores, in one call: the all-pairs scores of mpcgpu_sw_scores written to device memory, NormScore = Score / ((Li + Lj) / 2.0f)
+ * there (swdistmx.cpp:75-76), ScaleDistMx(true) and UPGMA5::Run(linkage) as above (swdistmx.cpp:123-126 with LINKAGE_Avg). No n x n matrix
+ * exists on either side; the four tree arrays come back, and the raw scores (n (n - 1) / 2 floats, the bits of mpcgpu_sw_scores) when
+ * scores != NULL. Refusals: those of mpcgpu_sw_scores for all pairs and of mpcgpu_upgma. mpcgpu_sw_info reports the scores' part. */
+int mpcgpu_sw_tree(mpcgpu_ctx *ctx, int linkage, uint32_t *left, uint32_t *right, float *left_len, float *right_len, float *scores);
+/* The last mpcgpu_upgma / mpcgpu_sw_tree call: out[0] n, out[1] 1 when the row state lived in LDS, out[2] device nanoseconds of transform and
+ * initialisation (for mpcgpu_sw_tree with the normalisation), out[3] device nanoseconds of the join loop (hipEvents). */
+int mpcgpu_upgma_info(mpcgpu_ctx *ctx, uint64_t out[4]);
+/* out[0] = Min, out[1] = Max as the last call's scaling transform found them (the values of ScaleDistMx's "Re-scaling" log line,
+ * upgma5.cpp:536; the scaled extremes of upgma5.cpp:561 follow from them: the transform is monotone). Refused when the last tree was built
+ * without a scaling transform. */
+int mpcgpu_upgma_scale(mpcgpu_ctx *ctx, float out[2]);
 
 /* ---- EA of a list of pairs, nothing else: the distance matrix over consensus sequences (kernels_postea.h, mpcgpu_ea.inc) ----------------
  * ea[q] = the float AlignPairFlat returns for (seq1[q], seq2[q]) — CalcAlnFlat's score over the dense thresholded posterior divided by

@@ -23,6 +23,7 @@ SYMBOLS = [
     "mpcgpu_work_get", "mpcgpu_synchronize", "mpcgpu_relax_info", "mpcgpu_shard_entries",
     "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch", "mpcgpu_store_epoch",
     "mpcgpu_sw_set_scores", "mpcgpu_sw_scores", "mpcgpu_sw_info", "mpcgpu_sw_bins", "mpcgpu_ea_scores", "mpcgpu_ea_info", "mpcgpu_ea_wide_info",
+    "mpcgpu_upgma", "mpcgpu_sw_tree", "mpcgpu_upgma_info", "mpcgpu_upgma_scale",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
     "mpcgpu_group_transport", "mpcgpu_group_set_hmm", "mpcgpu_group_set_seqs", "mpcgpu_group_set_mega",
     "mpcgpu_group_calc_posteriors", "mpcgpu_group_cons_iter",
@@ -109,6 +110,10 @@ def load(lib_path=None):
     L.mpcgpu_ea_scores.argtypes = [vp, u64, vp, vp, vp]
     L.mpcgpu_ea_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_ea_wide_info.argtypes = [vp, C.POINTER(u64)]
+    L.mpcgpu_upgma.argtypes = [vp, u32, vp, i32, i32, vp, vp, vp, vp]
+    L.mpcgpu_sw_tree.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.mpcgpu_upgma_info.argtypes = [vp, C.POINTER(u64)]
+    L.mpcgpu_upgma_scale.argtypes = [vp, C.POINTER(C.c_float)]
     L.mpcgpu_relax_info.argtypes = [vp, C.c_char_p, u32, C.POINTER(i32)]
     L.mpcgpu_group_create.argtypes = [C.POINTER(vp), u32, vp]
     L.mpcgpu_group_destroy.argtypes = [vp]
@@ -597,6 +602,51 @@ class MpcGpu:
         out = (C.c_uint64 * 4)()
         self._ck(self.L.mpcgpu_ea_wide_info(self.h, out))
         return tuple(int(x) for x in out)
+
+    UPGMA_TRANSFORMS = {"none": 0, "scale": 1, "scale_dist": 2, "ea": 3}
+    UPGMA_LINKAGES = {"avg": 0, "min": 1, "max": 2, "biased": 3}
+
+    def upgma(self, n, dist, transform="none", linkage="avg"):
+        """UPGMA5's tree of n leaves from the n (n - 1) / 2 distances of the pairs i < j in InitPairs order (what sw_scores / ea_scores
+        return). transform: "none", "scale" (ScaleDistMx, input is a similarity), "scale_dist" (input is a distance), "ea" (1 - d) or its
+        number; linkage: "avg", "min", "max", "biased" or its number -> (left, right, left_len, right_len), n - 1 entries each, the
+        arrays UPGMA5::Run hands to Tree::Create; the root is node n - 2"""
+        d = np.ascontiguousarray(dist, np.float32)
+        n = int(n)
+        assert d.ndim == 1 and (n < 2 or n > 65536 or len(d) == n * (n - 1) // 2)
+        k = max(n - 1, 1) if n <= 65536 else 1
+        left, right = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        ll, rl = np.zeros(k, np.float32), np.zeros(k, np.float32)
+        self._ck(self.L.mpcgpu_upgma(self.h, n, d.ctypes.data, self.UPGMA_TRANSFORMS.get(transform, transform), self.UPGMA_LINKAGES.get(linkage, linkage),
+                                     left.ctypes.data, right.ctypes.data, ll.ctypes.data, rl.ctypes.data))
+        return left[:n - 1], right[:n - 1], ll[:n - 1], rl[:n - 1]
+
+    def sw_tree(self, linkage="avg", want_scores=False):
+        """the guide tree of CalcGuideTree_SW_BLOSUM62 for the registered sequences under the tables of sw_set_scores, in one device
+        call: all-pairs scores, normalisation by the mean length, ScaleDistMx, UPGMA5 -> (left, right, left_len, right_len) and, with
+        want_scores, the raw scores as sw_scores() returns them"""
+        n = len(self.lens)
+        k = max(n - 1, 1)
+        left, right = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        ll, rl = np.zeros(k, np.float32), np.zeros(k, np.float32)
+        sc = np.zeros(max(n * (n - 1) // 2, 1), np.float32) if want_scores else None
+        self._ck(self.L.mpcgpu_sw_tree(self.h, self.UPGMA_LINKAGES.get(linkage, linkage), left.ctypes.data, right.ctypes.data, ll.ctypes.data, rl.ctypes.data,
+                                       None if sc is None else sc.ctypes.data))
+        tree = (left[:n - 1], right[:n - 1], ll[:n - 1], rl[:n - 1])
+        return tree + (sc[:n * (n - 1) // 2],) if want_scores else tree
+
+    def upgma_info(self):
+        """(n, 1 when the row state lived in LDS, device nanoseconds of transform + initialisation, device nanoseconds of the join loop)
+        of the last upgma / sw_tree call"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.L.mpcgpu_upgma_info(self.h, out))
+        return tuple(int(x) for x in out)
+
+    def upgma_scale(self):
+        """(Min, Max) the scaling transform of the last upgma / sw_tree call found (ScaleDistMx's "Re-scaling" line)"""
+        out = (C.c_float * 2)()
+        self._ck(self.L.mpcgpu_upgma_scale(self.h, out))
+        return np.float32(out[0]), np.float32(out[1])
 
     def build_post(self, seq1, seq2, p2c1, p2c2, C1, C2, w1=None, w2=None):
         """MPCFlat::BuildPost on the device store -> (C1, C2) float32 matrix (include/mpcgpu.h: mpcgpu_build_post)"""

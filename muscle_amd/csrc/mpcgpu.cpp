@@ -21,6 +21,7 @@
 #include "kernels_aln.h"
 #include "kernels_prog.h"
 #include "kernels_sw.h"
+#include "kernels_upgma.h"
 
 #include <algorithm>
 #include <chrono>
@@ -298,6 +299,15 @@ struct mpcgpu_ctx {
 		u64 pairs = 0, batches = 0, regrowths = 0, launches = 0;
 		u64 wide_pairs = 0, wide_batches = 0, wide_regrowths = 0, wide_launches = 0;
 	} ea;
+	// mpcgpu_upgma / mpcgpu_sw_tree (mpcgpu_upgma.inc): the triangle, the per-row state (m_MinDist, m_NearestNeighbor, m_NodeIndex), the tree
+	// arrays and m_Height, the partial extremes of the scaling pass, {Min, Max, status}; and what mpcgpu_upgma_info / _scale report of the last call
+	struct UpgmaState {
+		DevBuf d_tri, d_row, d_out, d_partial, d_stat;
+		u32 n = 0, lds = 0;
+		double ms_prep = 0, ms_join = 0;
+		bool scaled = false;
+		float smin = 0, smax = 0;
+	} up;
 };
 
 namespace {
@@ -755,6 +765,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->d_tiles2.release();
 	for (DevBuf *b : {&c->sw.d_let, &c->sw.d_off, &c->sw.d_tab, &c->sw.d_items, &c->sw.d_scores, &c->sw.d_queue, &c->sw.d_bnd}) b->release();
 	c->ea.d_ea.release(); c->ea.d_sort.release(); c->ea.h_ea.release();
+	for (DevBuf *b : {&c->up.d_tri, &c->up.d_row, &c->up.d_out, &c->up.d_partial, &c->up.d_stat}) b->release();
 	c->ea.d_wkeys.release(); c->ea.d_wrs.release(); c->ea.d_wsrow.release(); c->ea.d_winfo.release();
 	if (c->ea.ev) (void)hipEventDestroy(c->ea.ev);
 	c->pad_seg.release(); release_windows(c);
@@ -1048,6 +1059,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *c) { return c ? c->npairs : 0; }
 #include "mpcgpu_joins.inc"
 #include "mpcgpu_sw.inc"
 #include "mpcgpu_ea.inc"
+#include "mpcgpu_upgma.inc"
 int mpcgpu_relax_info(mpcgpu_ctx *c, char *buf, uint32_t buflen, int *is_fallback)
 {
 	if (!c) return 1;

@@ -78,9 +78,12 @@ int mpcgpu_sw_set_scores(mpcgpu_ctx *c, const uint8_t letter_of_char[256], uint3
 	return 0;
 }
 
-int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const uint32_t *seq2, float *scores)
+extern "C++" {
+namespace {
+
+// mpcgpu_sw_scores; d_dst != NULL: the results also (scores == NULL: only) go to device memory at d_dst, pair q at d_dst[q] (mpcgpu_sw_tree)
+int sw_scores_run(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const uint32_t *seq2, float *scores, float *d_dst)
 {
-	if (!c) return 1;
 	mpcgpu_ctx::SwState &w = c->sw;
 	if (!w.have) return fail(c, "mpcgpu_sw_scores: call mpcgpu_sw_set_scores first");
 	if (c->n == 0) return fail(c, "mpcgpu_sw_scores: call mpcgpu_set_seqs / mpcgpu_set_seqs_registry first");
@@ -88,7 +91,7 @@ int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const
 	const bool all = seq1 == nullptr;
 	if (all && npairs != (u64)c->n * (c->n - 1) / 2)
 		return fail(c, "mpcgpu_sw_scores: all pairs of %u sequences are %llu pairs, not %llu", c->n, (unsigned long long)((u64)c->n * (c->n - 1) / 2), (unsigned long long)npairs);
-	if (npairs && !scores) return fail(c, "mpcgpu_sw_scores: NULL argument");
+	if (npairs && !scores && !d_dst) return fail(c, "mpcgpu_sw_scores: NULL argument");
 	const u32 LMAX = 65535;
 	if (all) {
 		for (u32 i = 0; i < c->n; ++i)
@@ -183,7 +186,8 @@ int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const
 			w.bin_items[b] += cnt; w.bin_groups[b] += grid;
 		}
 		HIPCHK(c, hipEventRecord(eb, c->stream));
-		HIPCHK(c, hipMemcpyAsync(scores + q0, w.d_scores.p, B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+		if (d_dst) HIPCHK(c, hipMemcpyAsync(d_dst + q0, w.d_scores.p, B * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+		if (scores) HIPCHK(c, hipMemcpyAsync(scores + q0, w.d_scores.p, B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(c, hipStreamSynchronize(c->stream));
 		float ms = 0;
 		HIPCHK(c, hipEventElapsedTime(&ms, ea, eb));
@@ -197,6 +201,15 @@ int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const
 		q0 += B;
 	}
 	return 0;
+}
+
+} // namespace
+} // extern "C++"
+
+int mpcgpu_sw_scores(mpcgpu_ctx *c, uint64_t npairs, const uint32_t *seq1, const uint32_t *seq2, float *scores)
+{
+	if (!c) return 1;
+	return sw_scores_run(c, npairs, seq1, seq2, scores, nullptr);
 }
 
 int mpcgpu_sw_info(mpcgpu_ctx *c, uint64_t out[6])
