@@ -336,3 +336,110 @@ __global__ void __launch_bounds__(64) build_post_rows_batch_kernel(const BuildPo
 		build_post_one_row<CH>(p, rows[2 * w + 1], lkey, lval);
 	}
 }
+
+// The same row over a record store in the LONG form (kernels_store.h): the body above statement by statement with the long blocks' decode
+// (second column masked, 32-bit distance, the long form's sentinel). Written beside it, not as a common function: the listing of
+// the kernels above stays what it was, instruction for instruction.
+template <int CH, class PARAMS> // 64 * CH >= C2: columns a lane accumulates in registers
+__device__ __forceinline__ void build_post_one_row_long(const PARAMS &p, u32 col1, u32 *lkey, float *lval)
+{
+	const u32 lane = threadIdx.x;
+	const u32 npairs = p.n1 * p.n2;
+	float acc[CH];
+#pragma unroll
+	for (int c = 0; c < CH; ++c) acc[c] = 0.0f; // buildpostflat.cpp:27-30
+	for (u32 ab0 = 0; ab0 < npairs; ab0 += 64u) {
+		const u32 ab = ab0 + lane;
+		const bool valid = ab < npairs;
+		const u32 a = valid ? ab / p.n2 : 0u, b = valid ? ab % p.n2 : 0u;
+		const u32 pos = valid ? p.c2p1[(u64)a * p.C1 + col1] : MPC_BPR_GAP;
+		const bool have = pos != MPC_BPR_GAP;
+		const u32 S = p.seq1[a], T = p.seq2[b];
+		const unsigned char *row0 = (const unsigned char *)mpc_rec_ptr(p.s, S, T) + 16 * (u64)(have ? pos : 0u);
+		// pass 1: stored entries of the row (a block's second entry is real unless it repeats the first column or is the
+		// empty-row sentinel; a block's first entry is real unless the row is empty)
+		u32 cnt = 0;
+		if (have) {
+			const unsigned char *blk = row0;
+			for (;;) {
+				const MpcQuad v = *(const MpcQuad *)blk;
+				const u32 c0 = v.z & 0xffffu, c1 = mpc_blk_col1<true>(v.w), dist = mpc_blk_dist<true>(v.z, v.w);
+				cnt += (c0 != MPC_PADL_SENTINEL ? 1u : 0u) + ((c1 != c0 && c1 != MPC_PADL_SENTINEL) ? 1u : 0u);
+				if (dist == 0u) break;
+				blk += dist;
+			}
+		}
+		u32 incl = cnt;
+		for (int d = 1; d < 64; d <<= 1) {
+			const u32 o = __shfl_up(incl, d);
+			if (lane >= (u32)d) incl += o;
+		}
+		const u32 total = mpc_wave_first(__shfl(incl, 63));
+		if (total > MPC_BPR_CAP) { // not expected for the joins the host sends here; reported, not guessed
+			if (lane == 0) *p.err = 1u;
+			continue;
+		}
+		// pass 2: the entries, in lane order = (a, b) order, rows' entries in column order
+		if (have && cnt) {
+			u32 at = incl - cnt;
+			const u32 *m2 = p.p2c2 + p.off2[b];
+			const float w12 = p.w1 ? p.w1[a] * p.w2[b] : 1.0f; // w1*w2 rounded first: buildpostflat.cpp:74 / :96
+			const unsigned char *blk = row0;
+			for (;;) {
+				const MpcQuad v = *(const MpcQuad *)blk;
+				const u32 c0 = v.z & 0xffffu, c1 = mpc_blk_col1<true>(v.w), dist = mpc_blk_dist<true>(v.z, v.w);
+				if (c0 != MPC_PADL_SENTINEL) {
+					lkey[at] = m2[c0];
+					lval[at] = p.w1 ? w12 * __uint_as_float(v.x) : __uint_as_float(v.x);
+					++at;
+				}
+				if (c1 != c0 && c1 != MPC_PADL_SENTINEL) {
+					lkey[at] = m2[c1];
+					lval[at] = p.w1 ? w12 * __uint_as_float(v.y) : __uint_as_float(v.y);
+					++at;
+				}
+				if (dist == 0u) break;
+				blk += dist;
+			}
+		}
+		MPC_WAVE_LDS_ORDER();
+		// the additions, strictly in list order
+		for (u32 e = 0; e < total; ++e) {
+			const u32 k = mpc_wave_first(lkey[e]);
+			const float v = lval[e];
+			const u32 ch = k >> 6;
+			const bool mine = (k & 63u) == lane;
+#pragma unroll
+			for (int c = 0; c < CH; ++c)
+				if (ch == (u32)c) acc[c] = mine ? acc[c] + v : acc[c]; // ch is wave-uniform: scalar branches
+		}
+		MPC_WAVE_LDS_ORDER();
+	}
+	float *out = p.post + (u64)col1 * p.C2;
+#pragma unroll
+	for (int c = 0; c < CH; ++c)
+		if ((u32)c * 64u + lane < p.C2) out[(u32)c * 64u + lane] = acc[c];
+}
+
+// The two kernels above over a record store in the long form (kernels_store.h): the same body, the long form's block decode.
+template <int CH>
+__global__ void __launch_bounds__(64) build_post_rows_long_kernel(BuildPostRowsParams p)
+{
+	MPC_DYN_SMEM(smem_raw);
+	u32 *lkey = (u32 *)smem_raw;
+	float *lval = (float *)(smem_raw + 4 * MPC_BPR_CAP);
+	for (u32 col1 = blockIdx.x; col1 < p.C1; col1 += gridDim.x) build_post_one_row_long<CH>(p, col1, lkey, lval);
+}
+template <int CH>
+__global__ void __launch_bounds__(64) build_post_rows_batch_long_kernel(const BuildPostRowsParams *batch, const u32 *rows, u32 nrows)
+{
+	MPC_DYN_SMEM(smem_raw);
+	u32 *lkey = (u32 *)smem_raw;
+	float *lval = (float *)(smem_raw + 4 * MPC_BPR_CAP);
+	for (u32 w = blockIdx.x; w < nrows; w += gridDim.x) {
+		const u32 C2 = batch[rows[2 * w]].C2;
+		if (CH == 8 ? C2 > 512u : C2 <= 512u) continue;
+		const BuildPostRowsParams p = batch[rows[2 * w]];
+		build_post_one_row_long<CH>(p, rows[2 * w + 1], lkey, lval);
+	}
+}

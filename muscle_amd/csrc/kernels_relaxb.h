@@ -65,6 +65,19 @@ struct MpcRbBlocksCxx {
 #ifndef MPC_RB_HAVE_ASM
 typedef MpcRbBlocksCxx MpcRbBlocksAsm; // the emulator has the C++ statement only
 #endif
+// The two-list walk over a store in the LONG form (kernels_store.h: sequences above MPC_RV_MAXLEN, records above 4095 blocks): the
+// same tiles, staging and hop biases — a bias and a distance are bytes modulo 2^32, and a cell's two offsets are places in the step's
+// buffer, not in the record — with the long form's merge. The device and the emulator run this one statement.
+struct MpcRbLongCxx : MpcRbBlocksCxx {
+	template <int SET> __device__ __forceinline__ void merge(float &sum, u32 ia, u32 ib, u32 nia, u32 nib, u32 nidx, u32 bias_y)
+	{
+		const MpcQuad va = a[SET], vb = b[SET];
+		ib += hb;
+		a[SET ^ 1] = mpc_lds_load16(nia); b[SET ^ 1] = mpc_lds_load16(nib);
+		hb = mpc_lane_gather(bias_y, nidx);
+		mpc_rv_merge_long_cxx(sum, va, vb, ia, ib);
+	}
+};
 
 // The DIRECT-INDEX merge in C++ (MpcRbWinAsm, mpc_platform.h, is the hand-scheduled form): the X row is walked block by block,
 // every X entry (z, P) looks its partner up in the Y row's WINDOW (StoreParams::win): value = val[off + min(z - c0, span)] — a

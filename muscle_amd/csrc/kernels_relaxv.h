@@ -76,6 +76,29 @@ __device__ __forceinline__ void mpc_rv_merge_cxx(float &sum, MpcQuad va, MpcQuad
 		more = !((adv_a && da == 0u) || (adv_b && db == 0u));
 	}
 }
+// The same merge over blocks of the LONG form (kernels_store.h: the distance has 32 bits, its upper half in the upper half of the
+// second column word). A block is opened once when it is read — distance out, second column masked — and from there on the
+// statement above applies word for word: the same compares, the same two products and two adds per step, in the same order.
+__device__ __forceinline__ u32 mpc_rv_open_long(MpcQuad &v)
+{
+	const u32 d = mpc_blk_dist<true>(v.z, v.w);
+	v.w = mpc_blk_col1<true>(v.w);
+	return d;
+}
+__device__ __forceinline__ void mpc_rv_merge_long_cxx(float &sum, MpcQuad va, MpcQuad vb, u32 ia, u32 ib)
+{
+	u32 da = mpc_rv_open_long(va), db = mpc_rv_open_long(vb);
+	MPC_RV_TERMS(sum, va, vb);
+	bool adv_a = va.w <= vb.w, adv_b = vb.w <= va.w;
+	bool more = !((adv_a && da == 0u) || (adv_b && db == 0u));
+	while (more) {
+		if (adv_a) { ia += da; va = mpc_lds_load16(ia); da = mpc_rv_open_long(va); }
+		if (adv_b) { ib += db; vb = mpc_lds_load16(ib); db = mpc_rv_open_long(vb); }
+		MPC_RV_TERMS(sum, va, vb);
+		adv_a = va.w <= vb.w; adv_b = vb.w <= va.w;
+		more = !((adv_a && da == 0u) || (adv_b && db == 0u));
+	}
+}
 // one slot at a time, the next slot's first blocks in flight
 struct MpcRvBlocksCxx {
 	MpcQuad a[2], b[2];

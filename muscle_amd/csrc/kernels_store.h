@@ -110,6 +110,18 @@ struct StoreParams {
 #define MPC_WIN_MAXOFF 32767u  // and its value offset (15 bits)
 #define MPC_RB_HB 8u  // rows per index band of the band tables (overflow offsets here; cell offsets, y ranges: kernels_relaxb.h)
 #define MPC_PAD_SENTINEL 0x1fffu // larger than any column: sequences in the padded layout are <= 8191 long
+// The LONG form of the block records (a store with a sequence above MPC_RV_MAXLEN or a record above 4095 blocks; MPCGPU_RELAX_LONG):
+// block = {P0 bits, P1 bits, col0 | dist.lo << 16, col1 | dist.hi << 16} — the distance to the row's next block keeps its unit, bytes,
+// and gets 32 bits: its upper half rides in the upper half of the SECOND column word, which the 16-bit columns leave free. The empty
+// row's block is {0.0f, 0.0f, MPC_PADL_SENTINEL, MPC_PADL_SENTINEL}; entry positions (pos_f / pos_t) are 32-bit words in the same
+// allocation. Everything else — record order, rec_off, ovf_off, segments, the partial store — is the short form's. There are no window
+// records of such a store. Its kernels (var_build_long_kernel, commit_pairs_long_kernel, build_post_rows_long_kernel, relax_band_kernel
+// with MpcRbLongCxx) are written beside the short form's, which stay what they were instruction for instruction; a reader of the long
+// form decodes a block through the two functions below.
+#define MPC_PADL_SENTINEL 0xffffu // larger than any column: sequences in the long form are <= MPC_RL_MAXLEN long
+#define MPC_RL_MAXLEN 65534u      // columns keep 16 bits (stage A stops at 65 535 positions)
+template <bool LONG> __device__ __forceinline__ u32 mpc_blk_col1(u32 w) { return LONG ? (w & 0xffffu) : w; }
+template <bool LONG> __device__ __forceinline__ u32 mpc_blk_dist(u32 z, u32 w) { return LONG ? ((z >> 16) | (w & 0xffff0000u)) : (z >> 16); } // bytes
 
 __device__ __forceinline__ u64 mpc_pair_index(u32 n, u32 i, u32 j) // i<j, mpcflat.cpp:145-155 order
 {
@@ -294,6 +306,84 @@ __global__ void __launch_bounds__(64) var_build_kernel(StoreParams s)
 			rec_out[4 * unit + 2 + slot] = slot == 0 ? (c | (delta << 20)) : c; // << 16 and * 16: bytes
 			if (slot == 0 && within + 1 == cnt[r]) rec_out[4 * unit + 3] = c; // one-entry block: its column once more (P1 stays 0.0f)
 			pos[q] = (unsigned short)(unit * MPC_PAD_ROW + slot);
+		}
+		__syncthreads(); // s_start is reused by the next record
+	}
+}
+
+// The records of the LONG form (see MPC_PADL_SENTINEL above): var_build_kernel statement by statement with the long blocks and 32-bit
+// entry positions. Written beside it, not as a common function (the listing of var_build_kernel stays what it was). The two scans
+// of a row sequence of up to 65 534 positions do not fit the LDS: `scratch` holds 2*lcap1 u32 per workgroup.
+__global__ void __launch_bounds__(64) var_build_long_kernel(StoreParams s, u32 *scratch)
+{
+	u32 *s_start = scratch + 2ull * s.lcap1 * blockIdx.x; // entries before row a in the packed (unpadded) order
+	u32 *s_ovf = s_start + s.lcap1;                       // overflow blocks before row a
+	const int t = threadIdx.x;
+	const u64 total = (u64)s.n * s.n;
+	for (u64 b = blockIdx.x; b < total; b += gridDim.x) {
+		const u32 Z = (u32)(b / s.n), A = (u32)(b % s.n); // b == mpc_rec_index(n, A, Z)
+		const u32 LA = s.seq_len[A];
+		if (!mpc_need(s, A)) continue; // (wave-uniform) a partial store: this sequence has no records, no band entries, no positions
+		u32 *rec_out = mpc_rec_ptr(s, A, Z);
+		const u32 rec_end = mpc_rec_end(s, A, Z); // (not rec_off[b + 1]: the next record may open a segment)
+		const u32 units = rec_end - s.rec_off[b];
+		for (u32 q = t; q < units; q += 64) { // every block starts as an empty one
+			rec_out[4 * q] = 0u; rec_out[4 * q + 1] = 0u; rec_out[4 * q + 2] = MPC_PADL_SENTINEL; rec_out[4 * q + 3] = MPC_PADL_SENTINEL;
+		}
+		if (A == Z) { // empty matrix: conspairflat.cpp:39-40 skips Z == X and Z == Y
+			if (s.ovf_off) for (u32 q = t; q < s.nb1; q += 64) s.ovf_off[b * s.nb1 + q] = rec_end;
+			continue;
+		}
+		const bool fwd = A < Z;
+		const u64 k = fwd ? mpc_pair_pos(s, A, Z) : mpc_pair_pos(s, Z, A);
+		const u32 *rec = s.packed + s.pbase[k];
+		const u32 LX = fwd ? LA : s.seq_len[Z]; // rows of the stored (unordered) pair
+		const u32 LY = fwd ? s.seq_len[Z] : LA;
+		const u32 nnz = (u32)(s.vbase[k + 1] - s.vbase[k]);
+		const u32 *cnt = fwd ? rec : rec + LX; // rowcnt or colcnt, LA entries
+		u32 carry = 0, carry_o = 0;
+		for (u32 a0 = 0; a0 < LA; a0 += 64) {
+			const u32 a = a0 + t;
+			const u32 v = (a < LA) ? cnt[a] : 0;
+			const u32 nb = (v + MPC_PAD_ROW - 1) / MPC_PAD_ROW;
+			const u32 vo = nb > 1 ? nb - 1 : 0;
+			u32 incl = v, incl_o = vo;
+			for (int d = 1; d < 64; d <<= 1) {
+				const u32 o = __shfl_up(incl, d), oo = __shfl_up(incl_o, d);
+				if (t >= d) { incl += o; incl_o += oo; }
+			}
+			if (a < LA) {
+				s_start[a] = carry + incl - v;
+				s_ovf[a] = carry_o + incl_o - vo;
+			}
+			carry += __shfl(incl, 63);
+			carry_o += __shfl(incl_o, 63);
+		}
+		__syncthreads(); // empty blocks and scans are in place before the entries go in
+		if (s.ovf_off)
+			for (u32 q = t; q < s.nb1; q += 64)
+				s.ovf_off[b * s.nb1 + q] = MPC_RB_HB * q < LA ? s.rec_off[b] + LA + s_ovf[MPC_RB_HB * q] : rec_end;
+		const u32 *e = rec + LX + LY;
+		const u32 *rowv = e + 2 * (u64)nnz;
+		const u32 *tperm = rowv + nnz;
+		u32 *pos = (u32 *)(fwd ? s.pos_f : s.pos_t) + s.vbase[k]; // (u32 positions in the same two arrays)
+		for (u32 q = t; q < nnz; q += 64) {
+			const u32 pbits = e[2 * (u64)q];
+			const u32 col = e[2 * (u64)q + 1], row = rowv[q];
+			const u32 r = fwd ? row : col;       // row of this entry in M(A,Z)
+			const u32 rank = fwd ? q : tperm[q]; // its rank in M(A,Z)'s row-major order
+			const u32 c = fwd ? col : row;
+			const u32 within = rank - s_start[r];
+			const u32 j = within / MPC_PAD_ROW, slot = within % MPC_PAD_ROW;
+			const u32 nb = (cnt[r] + MPC_PAD_ROW - 1) / MPC_PAD_ROW;
+			const u32 ovf0 = LA + s_ovf[r]; // first overflow block of this row
+			const u32 unit = j == 0 ? r : ovf0 + (j - 1);
+			const u32 delta = j + 1 < nb ? (j == 0 ? ovf0 - r : 1u) : 0u; // blocks to the row's next block
+			rec_out[4 * unit + slot] = pbits;
+			const u32 db = delta * 16u; // bytes; both entries of a block know the row's next block: the second column word carries the upper half
+			rec_out[4 * unit + 2 + slot] = slot == 0 ? (c | (db << 16)) : (c | (db & 0xffff0000u));
+			if (slot == 0 && within + 1 == cnt[r]) rec_out[4 * unit + 3] = c; // one-entry block: its column once more (P1 stays 0.0f); the row's last, distance 0
+			pos[q] = unit * MPC_PAD_ROW + slot;
 		}
 		__syncthreads(); // s_start is reused by the next record
 	}
@@ -560,6 +650,32 @@ __global__ void __launch_bounds__(64) commit_pairs_kernel(StoreParams s, u64 k0,
 			// entry `pos` of a record = block pos / 2, slot pos % 2: its probability is dword block * 4 + slot
 			if (nx) { const u32 pf = s.pos_f[e]; rx[(pf >> 1) * 4u + (pf & 1u)] = pb; if (wx) wx[s.pos_wf[e]] = pb; }
 			if (ny) { const u32 pt = s.pos_t[e]; ry[(pt >> 1) * 4u + (pt & 1u)] = pb; if (wy) wy[s.pos_wt[e]] = pb; }
+		}
+	}
+}
+
+// The commit of a store in the LONG form: commit_pairs_kernel statement by statement with 32-bit entry positions and no window records
+// (written beside it: the listing of commit_pairs_kernel stays what it was).
+__global__ void __launch_bounds__(64) commit_pairs_long_kernel(StoreParams s, u64 k0, u64 k1, u64 e0, u64 e1, u64 own0, u64 own1, int lazy_packed)
+{
+	const u32 t = threadIdx.x;
+	for (u64 k = k0 + blockIdx.x; k < k1; k += gridDim.x) {
+		const u32 X = s.pair_x[k], Y = s.pair_y[k];
+		const bool nx = mpc_need(s, X), ny = mpc_need(s, Y);
+		const bool pk = !lazy_packed || (k >= own0 && k < own1);
+		if (!nx && !ny && !pk) continue;
+		const u64 vb = s.vbase[k], ve = s.vbase[k + 1];
+		const u64 a = vb > e0 ? vb : e0, b = ve < e1 ? ve : e1;
+		if (a >= b) continue;
+		const u32 LX = s.seq_len[X], LY = s.seq_len[Y];
+		u32 *ent = s.packed + s.pbase[k] + LX + LY;
+		u32 *rx = mpc_rec_ptr(s, X, Y), *ry = mpc_rec_ptr(s, Y, X);
+		for (u64 e = a + t; e < b; e += 64) {
+			const u32 pb = __float_as_uint(s.vnext[e]);
+			if (pk) ent[2 * (e - vb)] = pb;
+			// entry `pos` of a record = block pos / 2, slot pos % 2: its probability is dword block * 4 + slot
+			if (nx) { const u32 pf = ((const u32 *)s.pos_f)[e]; rx[(u64)(pf >> 1) * 4u + (pf & 1u)] = pb; }
+			if (ny) { const u32 pt = ((const u32 *)s.pos_t)[e]; ry[(u64)(pt >> 1) * 4u + (pt & 1u)] = pb; }
 		}
 	}
 }

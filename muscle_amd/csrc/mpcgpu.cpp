@@ -183,6 +183,7 @@ struct mpcgpu_ctx {
 	DevBuf d_tile_next, d_bp_in, d_aln_res, d_bp_seq, d_bp_map, d_bp_off, d_bp_coff, d_bp_keys, d_bp_vals, d_bp_tmp, d_bp_runs;
 	DevBuf d_tiles, d_pad, d_pos, d_aln_post, d_aln_tb, d_aln_rev, d_aln_bnd;
 	bool have_pad = false;       // variable-size dense records + relax_var_kernel (else: slabs + gather relax)
+	bool pad_long = false;       // the records are of the long form (kernels_store.h: 32-bit block distances and entry positions; band tiles only)
 	u32 pad_lcap1 = 0;           // longest sequence (LDS scratch of var_build_kernel)
 	DevBuf d_rec_off, d_sizes, d_tilefit;
 	u32 var_max_rec_blocks = 0;  // largest record, 16-byte blocks
@@ -573,7 +574,7 @@ void fill_store_params(mpcgpu_ctx *c, StoreParams &s)
 	s.pad = c->d_pad.as<u32>();
 	s.lcap1 = c->pad_lcap1;
 	s.pos_f = c->d_pos.as<unsigned short>();
-	s.pos_t = c->d_pos.as<unsigned short>() + c->total_entries;
+	s.pos_t = c->d_pos.as<unsigned short>() + (c->pad_long ? 2 : 1) * c->total_entries; // (the long form: u32 positions in the same two arrays)
 	s.rec_off = c->d_rec_off.as<u32>();
 	s.ovf_off = c->band_ok ? c->d_ovf_off.as<u32>() : nullptr;
 	s.nb1 = c->band_nb1;
@@ -652,6 +653,7 @@ static int build_slab_store(mpcgpu_ctx *c)
 	if (refresh_packed(c)) return 1; // (the slabs are built from the packed records)
 	c->own_k0 = 0; c->own_k1 = c->npairs; // (and hold everything: commits are complete from here on)
 	c->have_pad = false;
+	c->pad_long = false;
 	c->band_ok = false;
 	c->partial = false; // (the slabs hold every sequence: a partial store that falls back here is a complete one)
 	TimedSpan ts;

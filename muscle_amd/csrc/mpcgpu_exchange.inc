@@ -144,8 +144,9 @@ int mpcgpu_store_import_part(mpcgpu_ctx *c, uint32_t nshards, const uint64_t *k0
 	// Both are device paths with identical results.
 	c->have_pad = false;
 	{
-		// variable-size dense records + the LDS-tiled relax_var_kernel; a run beyond that layout's limits (sequences longer
-		// than 4095, records that do not fit the CU's LDS two at a time, ...) gets compact CSR slabs + the gather kernel
+		// variable-size dense records + the LDS-tiled kernels (sequences longer than 4095 or records of more than 4095 blocks: the
+		// records' long form, band tiles only); a run beyond that layout's limits (a band that no LDS holds, ...) gets compact CSR
+		// slabs + the gather kernel
 		// (MPCGPU_RELAX=gather forces it). Both are device paths with identical results.
 		const char *mode = getenv("MPCGPU_RELAX");
 		if (!(mode && !strcmp(mode, "gather"))) {
@@ -319,6 +320,10 @@ int mpcgpu_cons_commit_range(mpcgpu_ctx *c, uint64_t first, uint64_t count)
 			L.resize(w + 1);
 		}
 		const u64 pairs = std::min<u64>(kb, c->npairs) - ka;
+		if (c->pad_long) // the record store's long form: 32-bit entry positions
+			MPC_LAUNCH(commit_pairs_long_kernel, (u32)std::min<u64>(std::max<u64>(pairs, 1), (u64)c->prop.multiProcessorCount * 64), 64, 0, c->stream, sp, ka,
+				std::min<u64>(kb, c->npairs), (u64)first, (u64)(first + count), c->own_k0, c->own_k1, lazy ? 1 : 0);
+		else
 		MPC_LAUNCH(commit_pairs_kernel, (u32)std::min<u64>(std::max<u64>(pairs, 1), (u64)c->prop.multiProcessorCount * 64), 64, 0, c->stream, sp, ka,
 			std::min<u64>(kb, c->npairs), (u64)first, (u64)(first + count), c->own_k0, c->own_k1, lazy ? 1 : 0);
 	}

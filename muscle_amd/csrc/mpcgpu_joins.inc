@@ -316,7 +316,11 @@ static int build_post_rows(mpcgpu_ctx *c, const char *who, const JoinIn &j, LapT
 	if (trace_on()) { fprintf(stderr, "[mpcgpu] build_post %u x %u rows, %u x %u columns: row kernel, grid %u\n", j.n1, j.n2, j.C1, j.C2, grid); fflush(stderr); }
 	TimedSpan ts_rows;
 	if (span_begin(c, 5, &ts_rows)) return 1;
-	if (j.C2 <= 512u) MPC_LAUNCH(build_post_rows_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
+	if (c->pad_long) { // the record store's long form: the same body with the long blocks' decode
+		if (j.C2 <= 512u) MPC_LAUNCH(build_post_rows_long_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
+		else MPC_LAUNCH(build_post_rows_long_kernel<16>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
+	}
+	else if (j.C2 <= 512u) MPC_LAUNCH(build_post_rows_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
 	else MPC_LAUNCH(build_post_rows_kernel<16>, grid, 64, 8 * MPC_BPR_CAP, c->stream, rp);
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts_rows)) return 1;
@@ -518,7 +522,8 @@ static int run_join_chunk(mpcgpu_ctx *c, const std::vector<JoinIn> &jn, const u3
 	const u32 grid = (u32)std::min<u64>(all.row, (u64)c->prop.multiProcessorCount * 32u);
 	TimedSpan ts;
 	if (span_begin(c, 5, &ts)) return 1;
-	MPC_LAUNCH(build_post_rows_batch_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)all.row);
+	if (c->pad_long) MPC_LAUNCH(build_post_rows_batch_long_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)all.row);
+	else MPC_LAUNCH(build_post_rows_batch_kernel<8>, grid, 64, 8 * MPC_BPR_CAP, c->stream, (const BuildPostRowsParams *)(din + o_bp), (const u32 *)(din + o_rows), (u32)all.row);
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts)) return 1;
 	if (launch_aln_wave_batch(c, (const AlnParams *)(din + o_ap), nb, all.lds_rows)) return 1;

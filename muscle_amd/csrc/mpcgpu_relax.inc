@@ -509,8 +509,13 @@ template <int SL, int DG, class Merge> const void *relax_band_go(bool go, const 
 // hand-scheduled merge). merge_cxx: the compiler's code for the merge instead of the hand-scheduled one (A/B)
 // seg: the store lies in segments (StoreParams::pad_zbase) — the same four merges with the per-step base address in the staging; a
 // store of one segment never comes here, so what it launches is what it always launched
-static const void *relax_band_select(bool go, bool use_win, bool merge_cxx, int diag, bool seg, const RelaxBandParams &rp, u32 grid, size_t smem, hipStream_t st)
+// long_form: the records' long form (kernels_store.h) — its own merge, in either staging; no window records, no measurement kernels
+static const void *relax_band_select(bool go, bool use_win, bool merge_cxx, int diag, bool seg, bool long_form, const RelaxBandParams &rp, u32 grid, size_t smem, hipStream_t st)
 {
+	if (long_form) {
+		if (seg) return relax_band_go<kBandSlots, 0, MpcRbSegmented<MpcRbLongCxx> >(go, rp, grid, smem, st);
+		return relax_band_go<kBandSlots, 0, MpcRbLongCxx>(go, rp, grid, smem, st);
+	}
 	if (seg) {
 		if (use_win && merge_cxx) return relax_band_go<kBandSlotsWin, 0, MpcRbSegmented<MpcRbWinCxx> >(go, rp, grid, smem, st);
 		if (use_win) return relax_band_go<kBandSlotsWin, 0, MpcRbSegmented<MpcRbWinAsm> >(go, rp, grid, smem, st);
@@ -559,9 +564,11 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 	if (relax_diag_mode(c, &diag)) return 1;
 	const bool seg = sp.pad_zbase != nullptr || sp.win_zbase != nullptr;
 	if (seg && diag) return fail(c, "MPCGPU_RELAX_DIAG: the measurement kernels do not read a record store in segments");
+	const bool long_form = c->pad_long;
+	if (long_form && diag) return fail(c, "MPCGPU_RELAX_DIAG: the measurement kernels do not read a record store in the long form");
 	const char *merge_env = getenv("MPCGPU_RELAX_MERGE"); // "cxx": the compiler's code for the merge instead of the hand-scheduled one (A/B)
 	const bool merge_cxx = merge_env && !strcmp(merge_env, "cxx");
-	const void *fn = relax_band_select(false, g.use_win, merge_cxx, diag, seg, rp, 1, smem, c->stream);
+	const void *fn = relax_band_select(false, g.use_win, merge_cxx, diag, seg, long_form, rp, 1, smem, c->stream);
 	// (the two runtime queries cost a good fraction of a millisecond: once per context, kernel and LDS size — a -super7 run
 	// relaxes 400 small stores on every worker context)
 	int occ = 0;
@@ -575,7 +582,7 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 	const u32 grid = std::max(std::min<u32>(ntiles, g.cus * (u32)occ), 1u);
 	char kn[128];
 	snprintf(kn, sizeof(kn), "relax_band_kernel<%u, %u, 2, %d, %s%s%s>", kBandThreads, g.kernel_slots, diag, seg ? "MpcRbSegmented<" : "",
-		g.use_win ? (merge_cxx ? "MpcRbWinCxx" : "MpcRbWinAsm") : merge_cxx && !diag ? "MpcRbBlocksCxx" : "MpcRbBlocksAsm", seg ? "> " : "");
+		long_form ? "MpcRbLongCxx" : g.use_win ? (merge_cxx ? "MpcRbWinCxx" : "MpcRbWinAsm") : merge_cxx && !diag ? "MpcRbBlocksCxx" : "MpcRbBlocksAsm", seg ? "> " : "");
 	c->relax_kernel_name = kn;
 	if (trace_on()) {
 		char ord[24] = "pairs";
@@ -585,7 +592,7 @@ int relax_band(mpcgpu_ctx *c, const StoreParams &sp, u64 k0, u64 k1)
 	}
 	TimedSpan ts;
 	if (span_begin(c, 3, &ts)) return 1;
-	relax_band_select(true, g.use_win, merge_cxx, diag, seg, rp, grid, smem, c->stream);
+	relax_band_select(true, g.use_win, merge_cxx, diag, seg, long_form, rp, grid, smem, c->stream);
 	HIPCHK(c, hipGetLastError());
 	if (span_end(c, &ts)) return 1;
 #ifdef MPC_RELAX_DIAG_BUILD

@@ -83,7 +83,12 @@ int alloc_segments(mpcgpu_ctx *c, SegStore &st, const std::vector<u32> &z_first,
 int build_var_store(mpcgpu_ctx *c)
 {
 	const u32 n = c->n;
-	if (c->max_len > MPC_RV_MAXLEN) return 2;
+	// MPCGPU_RELAX_LONG: the records' LONG form (kernels_store.h) — taken by itself exactly where the short form's field widths end (a
+	// sequence above MPC_RV_MAXLEN, a record above 4095 blocks); 1: at any length (tests reach it with small shapes), 0: never (such
+	// stores get the CSR slabs and the gather kernel, as they did before the long form existed: A/B and escape hatch)
+	const int long_knob = env_int("MPCGPU_RELAX_LONG", -1);
+	c->pad_long = false;
+	if (c->max_len > MPC_RV_MAXLEN && (long_knob == 0 || c->max_len > MPC_RL_MAXLEN)) return 2;
 	StoreParams sp0;
 	fill_store_params(c, sp0);
 	const u64 nn = (u64)n * n;
@@ -98,7 +103,9 @@ int build_var_store(mpcgpu_ctx *c)
 	u32 max_rec = 0;
 	u64 run = 0; // all blocks, in 64 bits: block offsets are 32-bit inside a SEGMENT (64 GB of records each)
 	for (u64 b = 0; b < nn; ++b) { max_rec = std::max(max_rec, off[b + 1]); run += off[b + 1]; }
-	if (max_rec > 4095u) return 2; // a block's distance field holds 16 bits of bytes
+	if (max_rec > 4095u && long_knob == 0) return 2; // a block's distance field holds 16 bits of bytes
+	const bool long_form = long_knob == 1 || c->max_len > MPC_RV_MAXLEN || max_rec > 4095u;
+	if (long_form && (c->max_len > MPC_RL_MAXLEN || (u64)max_rec * 16 > 0xffffffffull)) return 2; // 16-bit columns, 32 bits of bytes
 	const u64 seg_limit = store_seg_limit();
 	std::vector<u32> seg_z, zend;
 	std::vector<u64> seg_blocks;
@@ -112,7 +119,8 @@ int build_var_store(mpcgpu_ctx *c)
 	auto fits = [&](bool fallback) { // every single pair: its two records, and its cells
 		return 2ull * max_rec * 16 <= var_buf_bytes(fallback) && (((u64)c->max_nnz + 63) & ~63ull) <= (u64)var_max_slots(fallback) * 1024u;
 	};
-	const bool fits_primary = fits(false), pairs_ok = fits_primary || fits(true);
+	// (the long form is for band tiles only: relax_var_kernel keeps a cell's two row offsets inside the records in 16 bits each)
+	const bool fits_primary = !long_form && fits(false), pairs_ok = !long_form && (fits_primary || fits(true));
 	const char *tiles_mode = getenv("MPCGPU_RELAX_TILES"); // "pairs": whole-record tiles of relax_var_kernel only; "band": band tiles whatever the size
 	// MPCGPU_RELAX_SMALL_PAIRS=<n> (default 0 = never; the drop-in binary sets 40): stores of <= n sequences whose pairs fit the
 	// whole-record tiles take those. A shrub of -super7 (<= 32 sequences, 412 of them in a 10 000-sequence run) is relaxed in 0.3 ms
@@ -128,10 +136,11 @@ int build_var_store(mpcgpu_ctx *c)
 	c->var_mixed = !fits_primary && pairs_ok;
 	if (!pairs_ok && !want_band) return 2; // (with pairs_ok false, band tiles may still be an option: relax_band)
 	if (nseg > 1 && !want_band) return 2;
-	const u64 pad_bytes = run * 16 + 4 * std::max<u64>(c->total_entries, 1);
+	const u64 pos_bytes = (long_form ? 8 : 4) * std::max<u64>(c->total_entries, 1); // pos_f then pos_t: u16 each, u32 in the long form
+	const u64 pad_bytes = run * 16 + pos_bytes;
 	// the records of an earlier store are kept where this cut fits them allocation by allocation; otherwise they go BEFORE the
 	// free-memory question is asked (a new cut of 70 GB beside the old one's segments would be refused, or fail in hipMalloc)
-	const bool held = segments_held(c->d_pad, c->pad_seg, seg_blocks) && 4 * std::max<u64>(c->total_entries, 1) <= c->d_pos.cap;
+	const bool held = segments_held(c->d_pad, c->pad_seg, seg_blocks) && pos_bytes <= c->d_pos.cap;
 	if (!segments_held(c->d_pad, c->pad_seg, seg_blocks)) { c->d_pad.release(); c->pad_seg.release(); }
 	size_t freeb = 0, totb = 0;
 	HIPCHK(c, hipMemGetInfo(&freeb, &totb));
@@ -144,10 +153,11 @@ int build_var_store(mpcgpu_ctx *c)
 		c->d_pad.release();
 		if (alloc_segments(c, c->pad_seg, seg_z, seg_blocks, zend)) return 1;
 	}
-	HIPCHK(c, c->d_pos.ensure(4 * std::max<u64>(c->total_entries, 1))); // pos_f then pos_t, u16 each
+	HIPCHK(c, c->d_pos.ensure(pos_bytes));
 	if (upload(c, c->d_rec_off, off)) return 1;
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // (the offsets live in the context: v_off; the wait orders the upload before the kernels that read the table)
 	c->have_pad = true;
+	c->pad_long = long_form;
 	c->pad_lcap1 = c->max_len;
 	c->var_max_rec_blocks = max_rec; c->var_total_blocks = run;
 	c->tiles_k0 = c->tiles_k1 = ~0ull;
@@ -180,9 +190,10 @@ int build_var_store(mpcgpu_ctx *c)
 			snprintf(b, sizeof(b), "variable-size dense records: %u x %u records, %.2f GB, mean %.0f B, largest %u B, band index of %u rows",
 				n, n, (double)run * 16 / 1e9, (double)run * 16 / (double)nn, max_rec * 16, (unsigned)MPC_RB_HB);
 			c->store_desc = b; // (the tiles and the kernel are described when the first relax has cut them: relax_band)
+			if (long_form) c->store_desc += ", band-long (32-bit block distances and entry positions)";
 			if (nseg > 1) c->store_desc += ", in " + std::to_string(nseg) + " segments of whole Z slabs";
 		}
-		if (!c->band_ok && (!pairs_ok || nseg > 1)) { c->have_pad = false; return 2; }
+		if (!c->band_ok && (!pairs_ok || nseg > 1)) { c->have_pad = false; c->pad_long = false; return 2; }
 		c->var_pairs_ok = pairs_ok && nseg == 1;
 	}
 	StoreParams sp;
@@ -194,7 +205,14 @@ int build_var_store(mpcgpu_ctx *c)
 	}
 	TimedSpan ts;
 	if (span_begin(c, 2, &ts)) return 1;
-	MPC_LAUNCH(var_build_kernel, (u32)std::min<u64>(nn, (u64)c->prop.multiProcessorCount * 32), 64, (size_t)std::max(sp.lcap1, 1u) * 8, c->stream, sp);
+	if (long_form) {
+		// the two row scans of a workgroup in global scratch (a row sequence of 65 534 positions: 512 KB), so fewer workgroups in flight;
+		// the record sizes have been read back: their buffer is free
+		const u32 grid = (u32)std::min<u64>(nn, (u64)c->prop.multiProcessorCount * 4);
+		HIPCHK(c, c->d_sizes.ensure(std::max<u64>((u64)grid * 2 * std::max(sp.lcap1, 1u) * 4, nn * 4)));
+		MPC_LAUNCH(var_build_long_kernel, grid, 64, 0, c->stream, sp, c->d_sizes.as<u32>());
+	}
+	else MPC_LAUNCH(var_build_kernel, (u32)std::min<u64>(nn, (u64)c->prop.multiProcessorCount * 32), 64, (size_t)std::max(sp.lcap1, 1u) * 8, c->stream, sp);
 	HIPCHK(c, hipGetLastError());
 	// ---- window records (the Y operand of the direct-index merge): a second copy of the store whose rows are looked up by column.
 	// Built when the rows are narrow — the windows then cost about what the blocks cost (1000 x L~400: 93 % of the rows span <= 4
@@ -202,7 +220,8 @@ int build_var_store(mpcgpu_ctx *c)
 	c->win_ok = false;
 	{
 		const char *form = getenv("MPCGPU_RELAX_FORM");
-		if (c->band_ok && !(form && !strcmp(form, "walk"))) {
+		// (the long form keeps block records for the Y operand: a window descriptor has 12 bits of column and 15 of value offset)
+		if (c->band_ok && !long_form && !(form && !strcmp(form, "walk"))) {
 			HIPCHK(c, c->d_sizes.ensure(nn * 4));
 			HIPCHK(c, c->d_tilefit.ensure(nn * 4)); // (scratch: value dwords per record)
 			HIPCHK(c, c->d_wflag.ensure(4));
