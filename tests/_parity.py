@@ -14,7 +14,7 @@ def bits(a):
 
 def run_lib(seqs, iters=2, lib_path=None, hmm_name="hmm_amino", expf_variant=-1, mega=None, info=None):
     """mega = dict(alpha, weight, lp, mx, profs): stage A on structure profiles (mpcgpu_set_mega); info: a dict that receives
-    stage_a_info"""
+    stage_a_info and, after the iterations, relax_info, relax_fallback and store_info"""
     s, t, m, i, thr = G.hmm_tables(hmm_name)
     g = MpcGpu(0, lib_path)
     g.set_hmm(s, t, m, i, thr, expf_variant)
@@ -34,6 +34,7 @@ def run_lib(seqs, iters=2, lib_path=None, hmm_name="hmm_amino", expf_variant=-1,
             stages.append(g.get_sparse_range())
         if info is not None:
             info["relax_info"], info["relax_fallback"] = g.relax_info()
+            info["store_info"] = g.store_info()
     g.close()
     return stages, ea
 

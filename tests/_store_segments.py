@@ -18,7 +18,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 HOOK = "MPCGPU_STORE_SEG_BLOCKS"
-FORMS = {"windows": {"MPCGPU_RELAX_WIN_PCT": "100000"}, "walk": {"MPCGPU_RELAX_FORM": "walk"}}
+# ("long": the long form of the block records, kernels_store.h: no window records, MpcRbSegmented<MpcRbLongCxx>)
+FORMS = {"windows": {"MPCGPU_RELAX_WIN_PCT": "100000"}, "walk": {"MPCGPU_RELAX_FORM": "walk"}, "long": {"MPCGPU_RELAX_LONG": "1"}}
+MERGE = {"windows": "MpcRbSegmented<MpcRbWin", "walk": "MpcRbSegmented<MpcRbBlocks", "long": "MpcRbSegmented<MpcRbLongCxx"}
 
 
 def family():
@@ -112,7 +114,7 @@ def _main(mode, out, lib_path):
     if mode == "stages":
         info = {}
         res["stages"], res["ea"] = P.run_lib(seqs, lib_path=lib_path, info=info)
-        res["info"], res["fallback"] = info["relax_info"], info["relax_fallback"]
+        res["info"], res["fallback"], res["window_bytes"] = info["relax_info"], info["relax_fallback"], info["store_info"]["window_bytes"]
     elif mode == "pairs":  # MPCGPU_RELAX_TILES=pairs on a store in segments: refused by name
         try:
             P.run_lib(seqs, lib_path=lib_path)
@@ -189,8 +191,33 @@ def check_stages(ref, got, plain, form, limit, what):
     want = ref.expect(limit, form == "windows")
     assert seg_counts(got["info"]) == want, (what, want, got["info"])
     assert want[0] > 1 and got["fallback"] == 0, (what, got["info"])
-    merge = "MpcRbSegmented<MpcRbWin" if form == "windows" else "MpcRbSegmented<MpcRbBlocks"
-    assert "relax_band_kernel" in got["info"] and merge in got["info"], got["info"]
+    assert "relax_band_kernel" in got["info"] and MERGE[form] in got["info"], got["info"]
+    assert ("band-long" in got["info"]) == ("band-long" in plain["info"]) == (form == "long"), (got["info"], plain["info"])
+    if form == "long":  # no window records, with the hook and without it
+        for run in (got, plain):
+            assert "window records" not in run["info"] and run["window_bytes"] == 0, (what, run["info"], run["window_bytes"])
+
+
+def same_joins(a, b, count=6):
+    """the joins of two runs of the child's "joins" mode: form, path, score and the three matrices of each, bit for bit"""
+    import _parity as P
+    assert len(a["joins"]) == len(b["joins"]) == count
+    for (bp, post, postw, path, sc, last), (bp2, post2, postw2, path2, sc2, last2) in zip(a["joins"], b["joins"]):
+        assert bp == bp2 and path == path2 and P.bits(sc) == P.bits(sc2), (bp, path, path2)
+        for x, y in ((post, post2), (postw, postw2), (last, last2)):
+            assert np.array_equal(P.bits(x), P.bits(y)), bp
+
+
+def check_lifetime(ref, got, form):
+    """the child's "lifetime" mode: all sequences, seven of them, all again on one context, each equal to the oracle, in segments"""
+    import _parity as P
+    subs = (ref.seqs, ref.seqs[2:9], ref.seqs)
+    wants = (ref.want, P.run_oracle(subs[1]), ref.want)
+    for (st, ea, (info, fallback)), want, sub in zip(got["runs"], wants, subs):
+        P.assert_same((st, ea), want, "n = %d" % len(sub))
+        assert seg_counts(info)[0] > 1 and fallback == 0, info
+        if form == "long":
+            assert "band-long" in info and MERGE["long"] in info and "window records" not in info, info
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@ def plain(emu, ref, tmp_path_factory):
 
 
 @pytest.mark.parametrize("cut", ["every", "few"])
-@pytest.mark.parametrize("form", ["windows", "walk"])
+@pytest.mark.parametrize("form", ["windows", "walk", "long"])
 def test_emu_every_boundary(emu, ref, plain, tmp_path, form, cut):
     limit = (ref.limits if form == "windows" else ref.limits_walk)[cut]
     if cut == "every":
@@ -56,3 +56,27 @@ def test_emu_segmented_staging_races(emu, ref, plain, tmp_path, finder):
 def test_emu_whole_record_tiles_are_refused_by_name(emu, ref, tmp_path):
     got = S.child("pairs", {S.HOOK: str(ref.limits["every"]), "MPCGPU_RELAX_TILES": "pairs"}, emu, tmp_path)
     assert got["error"] and "MPCGPU_RELAX_TILES=pairs" in got["error"] and "segments" in got["error"], got["error"]
+
+
+@pytest.mark.parametrize("seg", [False, True], ids=["plain", "segments"])
+def test_emu_long_partial_stores(emu, ref, tmp_path, seg):
+    """partial stores of the long form of the block records (MPCGPU_RELAX_LONG=1), one plain and one in segments: tests/_pair_order.py's
+    exchange between two contexts; band-long on both after every import"""
+    env = dict(S.FORMS["long"])
+    if seg:
+        env[S.HOOK] = str(ref.limits_walk["every"])
+    got = S.child("partial", env, emu, tmp_path)
+    assert len(got["infos"]) == 2
+    for info, fallback in got["infos"]:
+        assert "band-long" in info and (S.seg_counts(info)[0] > 1) == seg and fallback == 0, info
+
+
+def test_emu_long_joins_and_lifetime_in_segments(emu, ref, tmp_path):
+    """joins (rows and sort, plain and weighted) over a long store in segments equal those over the unsegmented one; release and regrowth"""
+    env = dict(S.FORMS["long"])
+    one = S.child("joins", env, emu, tmp_path)
+    env[S.HOOK] = str(ref.limits_walk["every"])
+    seg = S.child("joins", env, emu, tmp_path)
+    assert "band-long" in one["info"] and "band-long" in seg["info"] and S.seg_counts(seg["info"])[0] == ref.n and seg["fallback"] == 0, seg["info"]
+    S.same_joins(one, seg)
+    S.check_lifetime(ref, S.child("lifetime", env, emu, tmp_path), "long")
