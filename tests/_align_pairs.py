@@ -125,6 +125,17 @@ def regrowths(lens, cand, env):
     return n
 
 
+def regrowths_each(lens, cand, env):
+    """the overflow retries of a list that runs a pair per batch (MPCGPU_SCRATCH_GB=0; mpcgpu_ea.inc: ea_sublist()): only the batches
+    that hold an overflowing list are redone, and the room grows for the rest of the list once a batch was redone"""
+    capc, n = capc_of(lens, env), 0
+    full = max(a for a, _ in lens) * max(b for _, b in lens)
+    for k in cand:
+        while k > capc:
+            capc, n = min(2 * capc, full), n + 1
+    return n
+
+
 def predict(lens, env, cand=None):
     """the path of mpcgpu_align_pairs for pairs of these (LX, LY) under env: "short", "overflow" (short list whose candidate list
     overflowed: the general path redoes it; needs the oracle's candidate counts) or "general" (mpcgpu_joins.inc: align_pairs_small, mpcgpu_align_pairs)"""
@@ -160,7 +171,8 @@ def chunks_of(n, env):
 # ---- the oracle -------------------------------------------------------------------------------------------------------------
 def ap_oracle(h, x, y, mega=None, path=True):
     """AlignPairFlat_SparsePost (alignpairflat.cpp:3-27) on the oracle: mega = (O.make_mega(...), profile of x, profile of y) or None
-    -> dict(path, score, ea, off, val, cand: cells with Score >= MIN_SPARSE_SCORE, the candidate list the device keeps).
+    -> dict(path, score, ea, off, val, cand: cells with Score >= MIN_SPARSE_SCORE, the candidate list the device keeps, rows: the
+    cells of that list in each of the LX rows).
     path=False: the score alone (CalcAlnScoreFlat), as MPCFlat::CalcPosterior needs it (tests/_stage_a.py)"""
     if mega is None:
         F, B = O.fwd(h, x, y), O.bwd(h, x, y)
@@ -173,7 +185,7 @@ def ap_oracle(h, x, y, mega=None, path=True):
     sc, path = O.calc_aln(Pd) if path else (O.aln_score(Pd), None)
     off, val = O.sparse_from_post(Pd)
     return {"path": path, "score": np.float32(sc), "ea": np.float32(O.lib().orc_ea(sc, LX, LY)), "off": off, "val": val,
-            "cand": int(np.count_nonzero(Pd))}
+            "cand": int(np.count_nonzero(Pd)), "rows": np.count_nonzero(Pd, axis=1).astype(np.uint32)}
 
 
 _MEMO = {}

@@ -141,12 +141,7 @@ def route(name):
             continue
         sl, sc = [lens[k] for k in sub], [cand[k] for k in sub]
         if c["batches"] == "each":
-            # the room grows for the rest of the sub-list once a batch was redone
-            capc, full, re = A.capc_of(sl, c["env"]), max(a for a, _ in sl) * max(b for _, b in sl), 0
-            for n in sc:
-                while n > capc:
-                    capc, re = min(2 * capc, full), re + 1
-            tot.append((len(sub), len(sub), re))
+            tot.append((len(sub), len(sub), A.regrowths_each(sl, sc, c["env"])))
         else:
             tot.append((len(sub), 1, A.regrowths(sl, sc, c["env"])))
     (pn, bn, rn), (pw, bw, rw) = tot

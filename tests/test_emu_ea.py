@@ -18,7 +18,7 @@ def emu():
     return EMU_LIB
 
 
-@pytest.mark.parametrize("name", _ea.CASES)
+@pytest.mark.parametrize("name", _ea.CASES_BASE + _ea.CASES_PATHS)  # (CASES_DEVICE: their lists at a tenth of the long column are in CASES_PATHS)
 def test_emu_ea_case(emu, name):
     _ea.check_case(name, emu)
 
@@ -37,7 +37,7 @@ def test_emu_ea_other_thread_orders(emu, order):
     old = os.environ.get("EMU_SCHED")
     os.environ["EMU_SCHED"] = order
     try:
-        for name in ("tiny_1_1_2", "chaining", "regrowth"):
+        for name in ("tiny_1_1_2", "chaining", "regrowth", "persistent_small", "sort_cap_mixed", "post_batch_3", "batches_regrowth"):
             _ea.check_case(name, emu)
     finally:
         if old is None:
