@@ -43,7 +43,7 @@
 
 enum { MPC_UPGMA_T_NONE = 0, MPC_UPGMA_T_SCALE_SIM = 1, MPC_UPGMA_T_SCALE_DIST = 2, MPC_UPGMA_T_EA = 3 };
 enum { MPC_UPGMA_L_AVG = 0, MPC_UPGMA_L_MIN = 1, MPC_UPGMA_L_MAX = 2, MPC_UPGMA_L_BIASED = 3 };
-// status word of a run: 0, or one of these in the top byte with the join index below it
+// status word of a run: 0, or these in the top byte (both may be set: EA_RANGE is the refusal then) with the join index of NO_MIN below it
 #define MPC_UPGMA_ST_NO_MIN 0x01000000u   // no live row has a minimum below FLT_MAX (the reference asserts, upgma5.cpp:197-199)
 #define MPC_UPGMA_ST_EA_RANGE 0x02000000u // EA input outside 0 .. 1 (the reference dies, upgma5.cpp:512)
 
@@ -224,7 +224,9 @@ __global__ void __launch_bounds__(MPC_UPGMA_THREADS) upgma_join_kernel(UpgmaJoin
 		mpc_block_argmin(v, L, svA, siA);
 		const u32 R = L < n ? nn[L] : MPC_UPGMA_NONE;
 		if (L >= n || R >= n || R == L) { // the same in every lane
-			if (tid == 0) *p.status = MPC_UPGMA_ST_NO_MIN | k;
+			// beside what the transform kernel left, not over it: of an EA matrix that is out of range AND leaves no minimum the
+			// reference dies in FixEADistMx, and the host names that refusal first
+			if (tid == 0) atomicOr(p.status, MPC_UPGMA_ST_NO_MIN | k);
 			break;
 		}
 		// upgma5.cpp:212-271

@@ -3,12 +3,21 @@ equal, float bits of the branch lengths equal. Sizes: 2 (the first), 3, 65 (one 
 join kernel: a lane owns more than one row), each with every transform and linkage on a random matrix, a matrix of 4 distinct values (ties,
 the neighbour redirect, stale minima), one with negative entries and one with FLT_MAX entries; 65 and 1025 again with the row state in
 global memory. Where the reference itself asserts or dies (an EA value outside 0 .. 1; no distance below FLT_MAX left: a scaled matrix of
-one value, FLT_MAX under "max") the library must refuse by name."""
+one value, FLT_MAX under "max") the library must refuse by name, as the same kind of refusal and naming the same join.
+
+The named cases of tests/_upgma.py, which tests/test_upgma_table.py shows to reach their paths: 2100 leaves (rows in a second and a third
+stride of the join workgroup: Lmin, Rmin, ties across strides, redirects, stale picks) in LDS and in global memory; Min and Max where only a
+later pass of the grid-stride loops or a later round of the fold over the partials finds them (placed with the device's CU count);
+subnormals, zeros of both signs, NaN, inf, EA values at and just beyond the ends of 0 .. 1; outputs untouched by a refusal; the largest
+LDS request (12 288 leaves) and the first size in global memory with no knob set (12 289, which also strides upgma_init_kernel); one
+context reused across sizes and refusals; mpcgpu_sw_tree on 2100 sequences (upgma_sw_norm_kernel strides its rows)."""
 import hashlib
 import os
+import time
 
 import numpy as np
 import pytest
+import torch  # before the library is loaded: one HIP runtime in the process, the one the CU count is read from
 
 import _golden as G
 import _msa
@@ -102,6 +111,105 @@ def test_upgma_refusals_leave_the_context():
         assert g.store_epoch() == epoch and join() == before
     finally:
         g.close()
+
+
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+N = U.STRIDE_N["gpu"]
+
+
+@pytest.mark.parametrize("lds", [True, False])
+@pytest.mark.parametrize("linkage", U.LINKAGES)
+@pytest.mark.parametrize("kind", U.STRIDE_KINDS)
+def test_upgma_strides(kind, linkage, lds):
+    def run():
+        for transform in ("none", "scale"):
+            U.check_case(None, N, kind, transform, linkage, lds=lds)
+    run() if lds else _sw._with_env({"MPCGPU_UPGMA_LDS_ROWS": "0"}, run)
+
+
+def test_upgma_extremes():
+    cus = _cus()
+    m = U.n_tri(N)
+    assert U.passes(m, cus) >= 2 and U.fold_rounds(m, cus) >= 2, (cus, "a triangle of %d leaves no longer reaches a second pass / round" % N)
+    U.check_extremes(None, N, cus)
+
+
+def test_upgma_value_edges():
+    for n, kind, transform, linkage in U.edge_cases("gpu"):
+        U.check_case(None, n, kind, transform, linkage, lds=True)
+
+
+def test_upgma_value_edges_row_state_in_global_memory():
+    def run():
+        for n, kind, transform, linkage in U.edge_cases("gpu"):
+            if kind in ("subnormal", "nan_mid", "nan_all"):
+                U.check_case(None, n, kind, transform, linkage, lds=False)
+    _sw._with_env({"MPCGPU_UPGMA_LDS_ROWS": "0"}, run)
+
+
+def test_upgma_refusal_leaves_the_outputs():
+    U.check_refusal_leaves_outputs(None, U.EA_BAD_N["gpu"], ("ea_one_bad", "nan"), "ea", "avg", "ea_range")
+    U.check_refusal_leaves_outputs(None, U.SMALL_N["gpu"], "nan_all", "ea", "avg", "ea_range")
+    U.check_refusal_leaves_outputs(None, U.SMALL_N["gpu"], "nan_first", "scale", "avg", "no_min")
+
+
+@pytest.mark.parametrize("n,linkage,lds", [(12288, "avg", True), (12289, "biased", False)], ids=["lds_max", "global_natural"])
+def test_upgma_natural_cut(n, linkage, lds):
+    """no knob set: 12 288 leaves ask for 147 712 bytes of LDS, 12 289 run in global memory; both stride upgma_init_kernel's rows"""
+    assert "MPCGPU_UPGMA_LDS_ROWS" not in os.environ
+    cus = _cus()
+    assert U.join_lds(n) == (lds, 147712 if lds else 256) and U.init_row_passes(n, cus) >= 2, (n, cus)
+    t0 = time.time()
+    U.want(n, "random", "scale", linkage)
+    t1 = time.time()
+    U.check_case(None, n, "random", "scale", linkage, lds=lds)
+    info = U.ctx(None).upgma_info()
+    print("n %d: restatement %.1f s, device call with the triangle's copy %.2f s, device transform + init %.3f ms, joins %.3f ms"
+          % (n, t1 - t0, time.time() - t1, info[2] / 1e6, info[3] / 1e6))
+
+
+def test_upgma_reuse():
+    U.check_reuse(None, N, 65)
+
+
+def _sw_tree_strides_seqs():
+    """2100 sequences of 5 .. 40 positions, every seventh an exact copy of an earlier one: equal scores, equal distances"""
+    fam = make_family(N, 44, seed=77)
+    rng = np.random.default_rng(12)
+    seqs = [s[:int(ln)] for s, ln in zip(fam, rng.integers(5, 41, N))]
+    for i in range(7, N, 7):
+        seqs[i] = seqs[int(rng.integers(0, i))]
+    return seqs
+
+
+def test_sw_tree_strides():
+    seqs = _sw_tree_strides_seqs()
+    n = len(seqs)
+    assert n - 1 > 8 * _cus() and U.sw_norm_grid(n, _cus()) < n - 1  # upgma_sw_norm_kernel takes more than one row per workgroup
+    g = _sw.context(seqs)
+    try:
+        raw = g.sw_scores().copy()
+        lens = np.array([len(x) for x in seqs], np.uint32)
+        mean = np.concatenate([(lens[i] + lens[i + 1:]).astype(np.float32) / np.float32(2.0) for i in range(n - 1)])  # swdistmx.cpp:75
+        norm = (raw / mean).astype(np.float32)                                                                          # swdistmx.cpp:76
+        assert len(np.unique(norm)) < len(norm) - n  # the copies (and short sequences anyway): distances tie
+        for linkage in ("avg", "biased"):
+            left, right, ll, rl, sc = g.sw_tree(linkage=linkage, want_scores=True)
+            assert np.array_equal(_sw.bits(sc), _sw.bits(raw))
+            info = g.upgma_info()
+            assert info[0] == n and info[1] == 1
+            U.assert_same_tree((left, right, ll, rl), U.upgma(n, norm, "scale", linkage), "sw_tree " + linkage)
+            mn, mx = g.upgma_scale()
+            assert (U.float_bits(mn), U.float_bits(mx)) == tuple(U.float_bits(x) for x in U.device_min_max(norm))
+    finally:
+        g.close()
+
+
+def test_sw_tree_refuses_a_long_sequence():
+    U.check_long_sequence_refused(None)
 
 
 def _sw_tree_seqs():
