@@ -55,7 +55,12 @@ rm -f "$OUT/buildpostflat_ref.o"
 objcopy --weaken-symbol=_ZN6Super716IntraAlignShrubsEv "$REFOBJ/super7.o" "$OUT/super7_weak.o"
 # UClust::Search: ours (all word-count hits aligned in one library call); AlignPairFlat / AlignPairFlat_SparsePost: ours
 # (alignpairflat.o is not linked)
-objcopy --weaken-symbol=_ZN6UClust6SearchEjRNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEE "$REFOBJ/uclust.o" "$OUT/uclust_weak.o"
+# UClust::Run: ours too (the loop by windows, one mpcgpu_search_pairs call per window); the reference's body stays reachable under a
+# second, global name at the same address, UClust_Run_ref (MUSCLE_GPU_UCLUST_WINDOW=0 and unset call it)
+UCSYM=_ZN6UClust3RunER13MultiSequencef
+read -r UCVAL UCSEC < <(objdump -t "$REFOBJ/uclust.o" | awk -v s="$UCSYM" '$NF == s && $2 == "g" { print $1, $4 }')
+objcopy --weaken-symbol=_ZN6UClust6SearchEjRNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEE --weaken-symbol="$UCSYM" \
+  --add-symbol "UClust_Run_ref=$UCSEC:0x$UCVAL,global,function" "$REFOBJ/uclust.o" "$OUT/uclust_weak.o"
 # PProg::Run2: ours (independent joins of the guide tree side by side); AlignAndJoin and the rest of pprog2.o stay
 objcopy --weaken-symbol=_ZN5PProg4Run2ERKSt6vectorIjSaIjEES4_ "$REFOBJ/pprog2.o" "$OUT/pprog2_weak.o"
 # MPCFlat::CalcPosteriors: ours (a plain loop: the work of all pairs happens inside the first CalcPosterior call); the rest of mpcflat.o stays

@@ -383,6 +383,7 @@ std::atomic<unsigned long long> g_Nanos[T_COUNT];
 std::atomic<unsigned long long> g_Calls[T_COUNT];
 std::atomic<unsigned long long> g_SwKernelNanos; // device time of sw_kernel inside the "guide tree (SW)" row (mpcgpu_sw_info)
 std::atomic<unsigned long long> g_SwCells;
+std::atomic<unsigned long long> g_UcWindows, g_UcCuts, g_UcPairs, g_UcResent, g_UcCalls; // UClust::Run by windows (MUSCLE_GPU_UCLUST_WINDOW): the `uclust windows` row
 std::atomic<unsigned long long> g_UpgmaPrepNanos, g_UpgmaJoinNanos; // MUSCLE_GPU_UPGMA=1: device time of transform + initialisation and of the join loop (mpcgpu_upgma_info)
 // The timeline of ONE MPCFlat::Run (muscle -align): when the replaced functions were entered first / left last, in ns since process
 // start. What lies BETWEEN them is the reference's own host code — the row f4 of SURVEY.md 8 (CalcGuideTree = UPGMA5,
@@ -428,6 +429,8 @@ bool TimingOn()
 				if (g_UpgmaJoinNanos.load() != 0)
 					fprintf(stderr, "[muscle_gpu]   guide tree (SW): on the device also normalisation, scaling and row minima %.3f s, UPGMA5 join loop %.3f s\n",
 					  g_UpgmaPrepNanos.load()*1e-9, g_UpgmaJoinNanos.load()*1e-9);
+				fprintf(stderr, "[muscle_gpu] uclust windows %llu, cut %llu, pairs sent %llu, pairs sent for queries that were sent again %llu, library calls %llu\n",
+				  g_UcWindows.load(), g_UcCuts.load(), g_UcPairs.load(), g_UcResent.load(), g_UcCalls.load());
 				fprintf(stderr, "[muscle_gpu] posterior stage: computed %llu reused %llu\n", g_StagesComputed.load(), g_StagesReused.load());
 // (one MPCFlat::Run only: with the shrub workers of -super7 running many at once first-entered / last-left marks interleave)
 				const bool OneRun = g_Mark[M_POST_ENTER].load() != 0 && g_Mark[M_POST_ENTER].load() <= g_Mark[M_POST_EXIT].load() &&
@@ -1870,6 +1873,175 @@ uint UClust::Search(uint SeqIndex, string &Path)
 			return TopSeqIndexes[TopIndex];
 		}
 	return UINT_MAX;
+	}
+
+// UClust::Run (uclust.cpp:57-122) by WINDOWS. The reference searches every sequence, in length order, against the centroids that exist
+// when its turn comes: a true dependence, but most queries leave the index as it is. A window takes the next W sequences of the order,
+// makes every query's hit list with the reference's own m_US.SearchSeq on the index as it stands (truncated to MAX_REJECTS) and sends all
+// groups as ONE mpcgpu_search_pairs call — per query the first hit whose EA reaches the threshold, with its path (uclust.cpp:44-54). The
+// queries are then committed in order. A query's answer stands while the index has not changed since its list was made; once a query of
+// the window has become a centroid, every later query's list is made again on the current index and the answer stands only if the new list
+// equals the old one hit by hit, in the same order — SearchSeq orders ties through QuickSortOrderDesc over an array whose size is the index
+// size (usorter.cpp:107-126), so the order among OLD centroids can move too. Where the lists differ the window is CUT and that query opens
+// the next one. Tables, sequences (ALL of the input, by global label as AlignPairFlat finds them) and structure profiles go to the calling
+// thread's join context once per Run; the window calls pass indices only.
+// MUSCLE_GPU_UCLUST_WINDOW: 0 (and unset) = the reference's Run, kept in the binary as UClust_Run_ref (hostcxx/build_muscle_gpu.sh),
+// over the drop-in Search above; n >= 1 = the window size (1: the new call, no speculation).
+extern "C" void UClust_Run_ref(UClust *This, MultiSequence &InputSeqs, float MinEA);
+void UClust::Run(MultiSequence &InputSeqs, float MinEA)
+	{
+	const char *EnvW = getenv("MUSCLE_GPU_UCLUST_WINDOW");
+	const uint W = (EnvW != 0 && *EnvW != 0) ? (uint) std::max(atoi(EnvW), 0) : 0;
+	if (W == 0)
+		{
+		UClust_Run_ref(this, InputSeqs, MinEA);
+		return;
+		}
+// uclust.cpp:59-90
+	m_InputSeqs = &InputSeqs;
+	m_MinEA = MinEA;
+	m_US.Init();
+	const uint InputSeqCount = m_InputSeqs->GetSeqCount();
+	const uint GSICount = GetGlobalMSSeqCount();
+	vector<uint> GSIToInputSeqIndex(GSICount, UINT_MAX);
+	for (uint SeqIndex = 0; SeqIndex < InputSeqCount; ++SeqIndex)
+		{
+		const string Label = string(m_InputSeqs->GetLabel(SeqIndex));
+		uint GSI = GetGSIByLabel(Label);
+		asserta(GSI < GSICount);
+		asserta(GSIToInputSeqIndex[GSI] == UINT_MAX);
+		GSIToInputSeqIndex[GSI] = SeqIndex;
+		}
+	uint CentroidCount = 0;
+	uint MemberCount = 0;
+	m_SeqIndexToCentroidSeqIndex.clear();
+	m_SeqIndexToPath.clear();
+	m_SeqIndexToCentroidSeqIndex.resize(InputSeqCount, UINT_MAX);
+	m_SeqIndexToPath.resize(InputSeqCount);
+	vector<uint> Order;
+	InputSeqs.GetLengthOrder(Order);
+	uint LastLength = UINT_MAX;
+	const float MinEE = (1 - m_MinEA);
+// once per Run: tables, registry (registry index = input sequence index), profiles
+	JoinCtx &J = JoinOfThisThread();
+	std::lock_guard<std::mutex> Guard(J.m_Mu);
+	mpcgpu_ctx *Ctx = J.m_Ctx;
+	vector<uint32_t> Lens;
+		{
+		Stopwatch SW(T_PAIRS_PREP);
+		vector<const uint8_t *> Ptrs;
+		vector<string> Labels;
+		for (uint SeqIndex = 0; SeqIndex < InputSeqCount; ++SeqIndex)
+			{
+			const string &Label = m_InputSeqs->GetSequence(SeqIndex)->m_Label;
+			const Sequence &Seq = GetGlobalInputSeqByLabel(Label); // calcpost.cpp:6-7,25-26 look the sequences up by global label
+			Labels.push_back(Label);
+			Ptrs.push_back(Seq.GetBytePtr());
+			Lens.push_back(Seq.GetLength());
+			}
+		if (InputSeqCount > 0)
+			{
+			GPUCHK(mpcgpu_set_hmm(Ctx, PairHMM::m_StartScore, &PairHMM::m_TransScore[0][0],
+			  &PairHMM::m_MatchScore[0][0], PairHMM::m_InsScore, MIN_SPARSE_SCORE, -1));
+			GPUCHK(mpcgpu_set_seqs_registry(Ctx, InputSeqCount, Ptrs.data(), Lens.data()));
+			SetMega(Ctx, Labels, Lens);
+			}
+		}
+// uclust.cpp:26-41: the hit list of a query on the index as it stands
+	auto HitList = [&](uint SeqIndex, vector<uint> &Hits)
+		{
+		const Sequence *Seq = m_InputSeqs->GetSequence(SeqIndex);
+		vector<uint> TopWordCounts;
+		Hits.clear();
+		m_US.SearchSeq(Seq->GetBytePtr(), Seq->GetLength(), Hits, TopWordCounts);
+		asserta(SIZE(TopWordCounts) == SIZE(Hits));
+		if (SIZE(Hits) > MAX_REJECTS)
+			Hits.resize(MAX_REJECTS);
+		};
+	vector<vector<uint> > Lists;
+	vector<uint> Again;
+	vector<uint32_t> GroupFirst, Seqs1, Seqs2, PathLens, Accepted;
+	vector<char> PathBuf;
+	for (uint k = 0; k < InputSeqCount; )
+		{
+		const uint WinN = std::min(W, InputSeqCount - k);
+		Lists.resize(WinN);
+		GroupFirst.assign(1, 0);
+		Seqs1.clear();
+		Seqs2.clear();
+		uint32_t Stride = 1;
+		for (uint i = 0; i < WinN; ++i)
+			{
+			const uint SeqIndex = Order[k + i];
+			asserta(SeqIndex < InputSeqCount);
+			HitList(SeqIndex, Lists[i]);
+			for (uint t = 0; t < SIZE(Lists[i]); ++t)
+				{
+				Seqs1.push_back(SeqIndex);
+				Seqs2.push_back(Lists[i][t]);
+				Stride = std::max(Stride, Lens[SeqIndex] + Lens[Lists[i][t]]);
+				}
+			GroupFirst.push_back((uint32_t) Seqs1.size());
+			}
+		Accepted.assign(WinN, UINT32_MAX);
+		PathLens.assign(WinN, 0);
+		++g_UcWindows;
+		g_UcPairs += Seqs1.size();
+		if (!Seqs1.empty())
+			{
+			Stopwatch SW(T_PAIRS_LIB);
+			PathBuf.resize(size_t(WinN)*Stride);
+			GPUCHK(mpcgpu_search_pairs(Ctx, WinN, GroupFirst.data(), Seqs1.data(), Seqs2.data(), m_MinEA, Stride, PathBuf.data(),
+			  PathLens.data(), Accepted.data(), 0, 0));
+			++g_UcCalls;
+			}
+// commit in order (uclust.cpp:91-121)
+		bool IndexChanged = false;
+		uint Done = WinN;
+		for (uint i = 0; i < WinN; ++i)
+			{
+			const uint SeqIndex = Order[k + i];
+			if (IndexChanged)
+				{
+				HitList(SeqIndex, Again);
+				if (Again != Lists[i])
+					{
+					++g_UcCuts;
+					for (uint r = i; r < WinN; ++r)
+						g_UcResent += Lists[r].size();
+					Done = i;
+					break;
+					}
+				}
+			const uint L = (uint) InputSeqs.GetSeqLength(SeqIndex);
+			asserta(L <= LastLength);
+			LastLength = L;
+			ProgressStep(k + i, InputSeqCount,
+			  "UCLUST %u seqs EE<%.2f, %u centroids, %u members",
+			  InputSeqCount, MinEE, CentroidCount, MemberCount);
+			string &Path = m_SeqIndexToPath[SeqIndex];
+			uint RepSeqIndex = UINT_MAX;
+			if (Accepted[i] != UINT32_MAX)
+				{
+				asserta(Accepted[i] < SIZE(Lists[i]));
+				RepSeqIndex = Lists[i][Accepted[i]];
+				Path.assign(PathBuf.data() + size_t(i)*Stride, PathLens[i]);
+				++MemberCount;
+				}
+			else
+				{
+				m_CentroidSeqIndexes.push_back(SeqIndex);
+				AddSeqToIndex(SeqIndex);
+				++CentroidCount;
+				RepSeqIndex = SeqIndex;
+				Path.clear();
+				IndexChanged = true;
+				}
+			m_SeqIndexToCentroidSeqIndex[SeqIndex] = RepSeqIndex;
+			}
+		asserta(Done > 0); // the first query of a window always commits
+		k += Done;
+		}
 	}
 
 // Super7::IntraAlignShrubs (super7.cpp:127-137): one MPCFlat::Run per shrub of <= shrub_size sequences. The reference runs

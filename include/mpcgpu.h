@@ -103,7 +103,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   shards of mpcgpu_store_import_part): mpcgpu_set_hmm, mpcgpu_set_seqs, mpcgpu_set_seqs_registry, mpcgpu_set_mega, an accepted
  *   mpcgpu_set_pair_order (the order the context already has included: it drops shard and store), mpcgpu_calc_posteriors,
  *   mpcgpu_build_store, mpcgpu_store_import, mpcgpu_store_import_part, mpcgpu_values_import, mpcgpu_cons_iter, mpcgpu_cons_commit,
- *   mpcgpu_cons_commit_range, the list stages mpcgpu_align_pairs and mpcgpu_align_msas and mpcgpu_post_scores (they take the
+ *   mpcgpu_cons_commit_range, the list stages mpcgpu_align_pairs and mpcgpu_search_pairs and mpcgpu_align_msas and mpcgpu_post_scores (they take the
  *   scratch and invalidate the all-pairs store), and mpcgpu_group_set_hmm, _set_seqs, _set_mega, _calc_posteriors, _cons_iter on
  *   every context of the group (they are made of the calls above).
  *   LEAVES IT: mpcgpu_store_epoch itself, mpcgpu_last_error, mpcgpu_version, mpcgpu_pair_count, mpcgpu_pair_position,
@@ -112,7 +112,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *ctx); /* n(n-1)/2 */
  *   mpcgpu_values_export, mpcgpu_get_ea, mpcgpu_get_nnz, mpcgpu_get_sparse, mpcgpu_get_sparse_range, mpcgpu_get_list_sparse,
  *   mpcgpu_calc_aln, mpcgpu_align_alns, mpcgpu_align_alns_w, mpcgpu_align_alns_batch, mpcgpu_build_post, mpcgpu_get_last_post,
  *   mpcgpu_timers_reset, _enable, _get, mpcgpu_work_get, mpcgpu_stage_a_info, mpcgpu_stage_a_chain_bins, mpcgpu_stage_a_coop_info, mpcgpu_stage_a_fuse_info, mpcgpu_post_info,
- *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_synchronize, mpcgpu_sw_set_scores, mpcgpu_sw_scores, mpcgpu_sw_info and mpcgpu_sw_bins (tables, letters,
+ *   mpcgpu_store_info, mpcgpu_relax_info, mpcgpu_search_info, mpcgpu_synchronize, mpcgpu_sw_set_scores, mpcgpu_sw_scores, mpcgpu_sw_info and mpcgpu_sw_bins (tables, letters,
  *   work lists and results of the local-alignment scores live in buffers of their own: shard, store, values and the stage-A scratch are
  *   neither read nor written), mpcgpu_ea_scores and mpcgpu_ea_info (the call runs stage A's sweeps in stage A's scratch, which holds nothing
  *   between calls, and keeps its results in buffers of its own: shard, store, values and the results of the last stage A are neither read
@@ -336,6 +336,35 @@ int mpcgpu_align_pairs(mpcgpu_ctx *ctx, uint32_t npairs, const uint32_t *seq1, c
 /* MySparseMx::FromPost (mysparsemx.cpp:115-152) of pair q of the LAST list stage on this context (mpcgpu_align_pairs of at most 256
  * pairs, mpcgpu_align_msas): nnz, offsets[LX+1], values (8 bytes per entry; capacity from a first call with values == NULL). */
 int mpcgpu_get_list_sparse(mpcgpu_ctx *ctx, uint32_t q, uint32_t *nnz, uint32_t *offsets, void *values);
+
+/* The loop of UClust::Search (uclust.cpp:44-54) for a LIST of queries (kernels_search.h, mpcgpu_search.inc): the reference aligns a query's
+ * word-count hits one after the other with AlignPairFlat and keeps the path of the first whose EA reaches the threshold. Group g holds the
+ * candidate pairs [group_first[g], group_first[g + 1]) of registered sequences in the order they are to be tried (group_first: ngroups + 1
+ * entries, ascending from 0; an empty group is allowed).
+ *   ea[q]        (all pairs; may be NULL) the float mpcgpu_align_pairs returns for the pair, bit for bit
+ *   accepted[g]  the smallest t with ea[group_first[g] + t] >= min_ea — the reference's own comparison, so a NaN never qualifies —, UINT32_MAX
+ *                when no candidate qualifies
+ *   paths (ngroups slots of path_stride bytes), pathlens[g], scores[g] (may be NULL): path and CalcAlnFlat score of the accepted pair, the
+ *                bytes mpcgpu_align_pairs writes; pathlens[g] = 0 for a group without one
+ * ONLY THE ACCEPTED PAIRS get a dense posterior and a trace-back: a pair's EA is known after the finishing kernel. The list runs in chunks
+ * of MPCGPU_SEARCH_CHUNK pairs (512; at most 1024) that may end inside a group — a group that has its hit enters later chunks with nothing
+ * to try; the result does not depend on the cut. A chunk that satisfies what mpcgpu_align_pairs asks of a short list (no row-block pair, every
+ * alignment a one-wave alignment, the row-list finishing kernel) runs FUSED: sweeps, finishing kernel, search_pick_kernel (a wavefront per
+ * group folds its candidates' EAs), then the dense build and the one-wave alignment indirectly — a workgroup per group reads the pick on the
+ * device and leaves when there is none — on one stream with one wait. Every other chunk, a fused chunk whose candidate room overflowed, and
+ * every chunk under MPCGPU_SEARCH_FUSED=0 takes the GENERAL route: stage A as mpcgpu_align_pairs runs it, the EAs read back, the picks made
+ * on the host, dense posteriors and alignments for the picked pairs only. Same bits on both.
+ * A list stage like mpcgpu_align_pairs: it moves the store epoch, takes the scratch and invalidates an all-pairs store. It keeps no sparse
+ * matrices: mpcgpu_get_list_sparse after it is refused by name.
+ * Refused by name before any device work, the context left as it was: no sequences; a NULL argument other than scores / ea; a group_first
+ * that does not ascend from 0; an index outside the set; a path_stride smaller than LX + LY of a candidate; a pair beyond
+ * mpcgpu_align_pairs' envelope (LX * LY * 5 + 100 > INT_MAX). */
+int mpcgpu_search_pairs(mpcgpu_ctx *ctx, uint32_t ngroups, const uint32_t *group_first, const uint32_t *seq1, const uint32_t *seq2,
+                        float min_ea, uint32_t path_stride, char *paths, uint32_t *pathlens, uint32_t *accepted, float *scores, float *ea);
+/* The last mpcgpu_search_pairs call: out[0] groups, out[1] pairs, out[2] pairs whose dense posterior and trace-back were handed out (= the
+ * accepted groups, on both routes: the saving), out[3] chunks, out[4] chunks on the general route, out[5] device nanoseconds of pick + dense
+ * posteriors + alignments (hipEvents). All 0 before the first call; a refused call leaves them. */
+int mpcgpu_search_info(mpcgpu_ctx *ctx, uint64_t out[6]);
 
 /* ---- guide tree from bare sequences: all-pairs local-alignment scores (kernels_sw.h, mpcgpu_sw.inc) ------------------------
  * Tables of the score-only Smith-Waterman below. Replaces what MakeBlosum62SMx builds per pair (blosumsmx.cpp:32-53: a letter pair

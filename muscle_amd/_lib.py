@@ -24,6 +24,7 @@ SYMBOLS = [
     "mpcgpu_set_pair_order", "mpcgpu_pair_position", "mpcgpu_plan_partition", "mpcgpu_plan_store_segments", "mpcgpu_store_import_part", "mpcgpu_store_complete", "mpcgpu_store_info", "mpcgpu_align_alns_batch", "mpcgpu_store_epoch",
     "mpcgpu_sw_set_scores", "mpcgpu_sw_scores", "mpcgpu_sw_info", "mpcgpu_sw_bins", "mpcgpu_ea_scores", "mpcgpu_ea_info", "mpcgpu_ea_wide_info",
     "mpcgpu_upgma", "mpcgpu_sw_tree", "mpcgpu_upgma_info", "mpcgpu_upgma_scale",
+    "mpcgpu_search_pairs", "mpcgpu_search_info",
     "mpcgpu_group_create", "mpcgpu_group_destroy", "mpcgpu_group_last_error", "mpcgpu_group_size", "mpcgpu_group_ctx",
     "mpcgpu_group_transport", "mpcgpu_group_set_hmm", "mpcgpu_group_set_seqs", "mpcgpu_group_set_mega",
     "mpcgpu_group_calc_posteriors", "mpcgpu_group_cons_iter",
@@ -91,6 +92,8 @@ def load(lib_path=None):
     L.mpcgpu_get_last_post.argtypes = [vp, u32, u32, vp]
     L.mpcgpu_align_pairs.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp, vp]
     L.mpcgpu_get_list_sparse.argtypes = [vp, u32, C.POINTER(u32), vp, vp]
+    L.mpcgpu_search_pairs.argtypes = [vp, u32, vp, vp, vp, C.c_float, u32, vp, vp, vp, vp, vp]
+    L.mpcgpu_search_info.argtypes = [vp, C.POINTER(u64)]
     L.mpcgpu_set_seqs_registry.argtypes = [vp, u32, vp, vp]
     L.mpcgpu_align_msas.argtypes = [vp, u32, vp, vp, u32, u32, vp, vp, vp, C.POINTER(u32), C.POINTER(C.c_float), vp]
     L.mpcgpu_timers_reset.argtypes = [vp]
@@ -537,6 +540,37 @@ class MpcGpu:
             self._ck(self.L.mpcgpu_get_list_sparse(self.h, q, C.byref(nz), off.ctypes.data, val.ctypes.data))
             sp.append((off, val[:2 * nz.value].copy()))
         return out, sp
+
+    def search_pairs(self, groups, min_ea):
+        """UClust::Search's loop for a list of queries (mpcgpu_search_pairs). groups: per query the candidate pairs (x, y) of registered
+        sequences in the order they are to be tried (a group may be empty) -> (accepted: per group the position of the first candidate
+        whose EA >= min_ea, or None; hits: per group (path, score) of that pair, or None; ea: float32 of every pair, groups back to back)"""
+        first = np.zeros(len(groups) + 1, np.uint32)
+        first[1:] = np.cumsum([len(g) for g in groups])
+        flat = [p for g in groups for p in g]
+        s1 = np.ascontiguousarray([x for x, _ in flat], np.uint32)
+        s2 = np.ascontiguousarray([y for _, y in flat], np.uint32)
+        ng, n = len(groups), len(flat)
+        nseq = len(self.lens)  # (an index outside the set is the library's to refuse)
+        stride = max([int(self.lens[a]) + int(self.lens[b]) for a, b in flat if a < nseq and b < nseq] + [1])
+        paths = np.zeros(max(ng, 1) * stride, np.uint8)
+        plen = np.zeros(max(ng, 1), np.uint32)
+        acc = np.zeros(max(ng, 1), np.uint32)
+        sc = np.zeros(max(ng, 1), np.float32)
+        ea = np.zeros(max(n, 1), np.float32)
+        self._ck(self.L.mpcgpu_search_pairs(self.h, ng, first.ctypes.data, s1.ctypes.data, s2.ctypes.data, float(np.float32(min_ea)), stride,
+                                            paths.ctypes.data, plen.ctypes.data, acc.ctypes.data, sc.ctypes.data, ea.ctypes.data))
+        accepted = [None if int(acc[g]) == 0xffffffff else int(acc[g]) for g in range(ng)]
+        hits = [None if accepted[g] is None else (paths[g * stride:g * stride + int(plen[g])].tobytes().decode(), np.float32(sc[g])) for g in range(ng)]
+        assert all(int(plen[g]) == 0 for g in range(ng) if accepted[g] is None)
+        return accepted, hits, ea[:n].copy()
+
+    def search_info(self):
+        """(groups, pairs, pairs whose dense posterior and trace-back ran, chunks, chunks on the general route, device nanoseconds of
+        pick + dense posteriors + alignments) of the last search_pairs call"""
+        out = (C.c_uint64 * 6)()
+        self._ck(self.L.mpcgpu_search_info(self.h, out))
+        return tuple(int(x) for x in out)
 
     def sw_set_scores(self, letter_of_char, sub, open_score, ext_score):
         """tables of sw_scores: letter of every byte value (256 x uint8), alpha x alpha substitution scores (a letter >= alpha scores 0

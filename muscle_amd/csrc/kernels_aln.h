@@ -315,6 +315,88 @@ __global__ void __launch_bounds__(256) dense_post_raw_kernel(DensePostRawParams 
 	}
 }
 
+// ---- the INDIRECT forms (mpcgpu_search_pairs, mpcgpu_search.inc): one workgroup per SLOT, and which pair of the batch a slot serves is
+// read from pick[slot] on the device — MPC_PICK_NONE: the workgroup leaves at once. A slot is a group of candidate pairs of which at most
+// one is kept (uclust.cpp:44-54: the first hit whose EA reaches the threshold), chosen by search_pick_kernel (kernels_search.h) behind the
+// finishing kernel on the same stream: no dense matrix and no trace-back for the others, and nothing read back in between. Slot s's matrix
+// lies at out_off[s], sized by the host for the slot's largest LX x LY. The cell code is dense_post_kernel's, dense_post_raw_kernel's and
+// calc_aln_wave_body: same bits, same letters. The direct kernels above are left as they are (their listings do not move).
+#define MPC_PICK_NONE 0xffffffffu
+
+struct DensePostPickParams {
+	DensePostParams d; // out_off: per slot
+	const u32 *pick;   // per slot: pair of the batch, or MPC_PICK_NONE
+};
+
+__global__ void __launch_bounds__(256) dense_post_pick_kernel(DensePostPickParams p)
+{
+	const u32 q = p.pick[blockIdx.x];
+	if (q == MPC_PICK_NONE) return;
+	const u32 LX = p.d.seq_len[p.d.pair_x[q]], LY = p.d.seq_len[p.d.pair_y[q]];
+	const u32 c = p.d.cand_cnt[q];
+	if (c > p.d.capc) return; // an overflowed list: the host drops the chunk and redoes it (dense_post_kernel)
+	float *M = p.d.out + p.d.out_off[blockIdx.x];
+	const u64 cells = (u64)LX * LY;
+	for (u64 e = threadIdx.x; e < cells; e += blockDim.x) M[e] = 0.0f;
+	__syncthreads();
+	const u32 kshift = LX >= p.d.long_min ? MPC_KEY_ROW_SHIFT_LONG : MPC_KEY_ROW_SHIFT;
+	const u64 *cand = p.d.cand + (u64)q * p.d.capc;
+	for (u32 e = threadIdx.x; e < c; e += blockDim.x) {
+		const u64 v = cand[e];
+		const u32 key = (u32)(v >> 32);
+		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
+		M[(u64)row * LY + col] = __uint_as_float((u32)v);
+	}
+}
+
+// ... from the raw candidate lists (dense_post_raw_kernel): the host has zeroed the slots' matrices; workgroup b serves slab b % slabs of slot b / slabs
+struct DensePostRawPickParams {
+	DensePostRawParams r;
+	const u32 *pick;
+};
+
+__global__ void __launch_bounds__(256) dense_post_raw_pick_kernel(DensePostRawPickParams p)
+{
+	const u32 s = blockIdx.x / p.r.slabs, slab = blockIdx.x % p.r.slabs;
+	const u32 q = p.pick[s];
+	if (q == MPC_PICK_NONE) return;
+	const u32 LX = p.r.d.seq_len[p.r.d.pair_x[q]], LY = p.r.d.seq_len[p.r.d.pair_y[q]];
+	const u32 c = p.r.d.cand_cnt[q];
+	if (c > p.r.d.capc) return;
+	float *M = p.r.d.out + p.r.d.out_off[s];
+	const u32 kshift = mpc_key_shift(LX, p.r.d.long_min);
+	const u64 *cand = p.r.d.cand + (u64)q * p.r.d.capc;
+	for (u32 e = slab * blockDim.x + threadIdx.x; e < c; e += p.r.slabs * blockDim.x) {
+		const u64 v = cand[e];
+		const u32 key = (u32)(v >> 32);
+		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
+		const float pr = mpc_score_to_prob(__uint_as_float((u32)v), p.r.use_fma);
+		if (row < LX && col < LY) M[(u64)row * LY + col] = pr;
+	}
+}
+
+// the one-wave alignment of slot s's matrix: the AlnParams record calc_aln_wave_batch_kernel reads from the host is formed here, from the
+// picked pair's lengths. rec: a result record {u32 path length, f32 score, path} per slot, rec_stride apart; rev: rev_stride bytes per slot
+struct AlnPickParams {
+	const u32 *pick;
+	const u32 *pair_x, *pair_y, *seq_len;
+	const float *post;
+	const u64 *out_off;
+	char *rev; u32 rev_stride;
+	char *rec; u64 rec_stride;
+};
+
+__global__ void __launch_bounds__(64) calc_aln_wave_pick_kernel(AlnPickParams b)
+{
+	MPC_DYN_SMEM(smem_raw);
+	const u32 s = blockIdx.x;
+	const u32 q = b.pick[s];
+	if (q == MPC_PICK_NONE) return;
+	char *rec = b.rec + (u64)s * b.rec_stride;
+	const AlnParams p = {b.post + b.out_off[s], b.seq_len[b.pair_x[q]], b.seq_len[b.pair_y[q]], nullptr, b.rev + (u64)s * b.rev_stride, rec + 8, (u32 *)rec, (float *)(rec + 4)};
+	calc_aln_wave_body(p, smem_raw);
+}
+
 // ---- matrices wider than the LDS holds two DP rows of (calc_aln_kernel's limit: LY + 1 <= ~20 470 columns) ------------------
 // calc_aln_kernel with the columns swept in tiles of `tile` columns: a tile runs all LX rows with its two DP rows in LDS, then
 // the next tile does, and what crosses a tile's left edge is one value per row, S(i, a-1) of the tile's first column a: the

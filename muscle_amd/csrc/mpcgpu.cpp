@@ -2,7 +2,8 @@
 // kernels_fb.h (pair-HMM forward/backward, letter and structure-profile emissions), kernels_post.h (probabilities, sparsify, EA),
 // kernels_postea.h, kernels_postwea.h (probabilities and EA alone: a wave / a workgroup per pair),
 // kernels_store.h (packed records, padded / slab stores, gather relax, commit, export),
-// kernels_relaxv.h (LDS-tiled relax over variable-size records), kernels_aln.h (posterior-DP alignment + traceback) and
+// kernels_relaxv.h (LDS-tiled relax over variable-size records), kernels_aln.h (posterior-DP alignment + traceback), kernels_search.h (first
+// qualifying hit of a group of pairs) and
 // kernels_prog.h (MSA x MSA posterior build). Built by hipcc (-x hip) for gfx950. There is no CPU
 // implementation behind this API: without a HIP device mpcgpu_create() fails. rocPRIM's radix sort
 // (rocprim::radix_sort_pairs, called directly) is used for one bulk data-movement step (kernels_prog.h); everything else is
@@ -19,6 +20,7 @@
 #include "kernels_relaxv.h"
 #include "kernels_relaxb.h"
 #include "kernels_aln.h"
+#include "kernels_search.h"
 #include "kernels_prog.h"
 #include "kernels_sw.h"
 #include "kernels_upgma.h"
@@ -309,6 +311,19 @@ struct mpcgpu_ctx {
 		bool scaled = false;
 		float smin = 0, smax = 0;
 	} up;
+	// mpcgpu_search_pairs (mpcgpu_search.inc): the page-locked record of a chunk and its device copy, sizes / EA / flags of the chunk's pairs as the
+	// finishing kernel leaves them, the picks of the general route, the events around pick + dense + alignment, the largest dynamic LDS
+	// calc_aln_wave_pick_kernel has been allowed; last: the last list stage was a search (mpcgpu_get_list_sparse refuses); and what
+	// mpcgpu_search_info reports of the last call
+	struct SearchState {
+		HostBuf h;
+		DevBuf d_in, d_nnz, d_ea, d_flags, d_pick, d_off;
+		hipEvent_t ev0 = nullptr, ev1 = nullptr;
+		size_t aln_smem = 0;
+		bool last = false;
+		u64 groups = 0, pairs = 0, traced = 0, chunks = 0, general = 0;
+		double ms = 0;
+	} se;
 };
 
 namespace {
@@ -770,6 +785,10 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	for (DevBuf *b : {&c->up.d_tri, &c->up.d_row, &c->up.d_out, &c->up.d_partial, &c->up.d_stat}) b->release();
 	c->ea.d_wkeys.release(); c->ea.d_wrs.release(); c->ea.d_wsrow.release(); c->ea.d_winfo.release();
 	if (c->ea.ev) (void)hipEventDestroy(c->ea.ev);
+	c->se.h.release();
+	for (DevBuf *b : {&c->se.d_in, &c->se.d_nnz, &c->se.d_ea, &c->se.d_flags, &c->se.d_pick, &c->se.d_off}) b->release();
+	if (c->se.ev0) (void)hipEventDestroy(c->se.ev0);
+	if (c->se.ev1) (void)hipEventDestroy(c->se.ev1);
 	c->pad_seg.release(); release_windows(c);
 	if (c->ev_post) (void)hipEventDestroy(c->ev_post);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -1059,6 +1078,7 @@ uint64_t mpcgpu_pair_count(const mpcgpu_ctx *c) { return c ? c->npairs : 0; }
 #include "mpcgpu_stage_a.inc"
 #include "mpcgpu_exchange.inc"
 #include "mpcgpu_joins.inc"
+#include "mpcgpu_search.inc"
 #include "mpcgpu_sw.inc"
 #include "mpcgpu_ea.inc"
 #include "mpcgpu_upgma.inc"

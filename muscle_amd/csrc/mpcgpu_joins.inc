@@ -687,7 +687,7 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 	}
 	if (!post_rows_fits(g.LXmax, g.LYmax, 1024)) return 2;
 	c->have_shard = c->have_store = false;
-	c->shard_is_list = true;
+	c->shard_is_list = true; c->se.last = false;
 	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np);
 	c->list_q0 = 0; c->ap_x.clear(); c->ap_y.clear();
 	c->sh_k0 = 0; c->sh_k1 = np;
@@ -867,6 +867,7 @@ int mpcgpu_get_list_sparse(mpcgpu_ctx *c, uint32_t q, uint32_t *nnz, uint32_t *o
 {
 	if (!c) return 1;
 	if (!c->shard_is_list) return fail(c, "mpcgpu_get_list_sparse: no list stage holds pair %u", q);
+	if (c->se.last) return fail(c, "mpcgpu_get_list_sparse: the last list stage was mpcgpu_search_pairs, which keeps no sparse matrices (pair %u)", q);
 	HIPCHK(c, hipSetDevice(c->device));
 	// q indexes the list the CALLER passed. mpcgpu_align_pairs may have run that list in chunks (256 pairs, halved when stage A had to
 	// split one): the last stage then holds pairs [list_q0, list_q0 + list_x.size()) of it. A pair outside that window gets a stage

@@ -783,7 +783,7 @@ static int stage_a(mpcgpu_ctx *c, u64 np, const u32 *px, const u32 *py)
 {
 	HIPCHK(c, hipSetDevice(c->device));
 	c->have_shard = c->have_store = false;
-	c->shard_is_list = true;
+	c->shard_is_list = true; c->se.last = false;
 	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np); // mpcgpu_get_list_sparse
 	c->list_q0 = 0;
 	if (!c->ap_keep) { c->ap_x.clear(); c->ap_y.clear(); }
