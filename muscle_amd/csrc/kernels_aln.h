@@ -30,6 +30,79 @@ struct AlnParams {
 	float *score;      // out
 };
 
+// ---- what calc_aln_kernel and calc_aln_tiled_kernel (rows in LDS) share: a thread's columns are a + [l0, l1), column a + l lives in slot
+// l + slot of oldr / newr (calc_aln_kernel: a = 0, slot = column)
+// pass 1: maximum of T over my columns
+__device__ __forceinline__ float aln_lds_pass1(const float *oldr, const float *prow, u32 a, u32 l0, u32 l1, u32 slot)
+{
+	float run = 0.0f; // T_j >= 0 always (X >= 0), and S(i,0) = 0
+	for (u32 l = (a + l0 == 0 ? 1u : l0); l < l1; ++l) { // (column 0 has no B)
+		const float B = oldr[l + slot - 1] + prow[a + l - 1];
+		const float X = oldr[l + slot];
+		const float T = B >= X ? B : X;
+		run = T >= run ? T : run;
+	}
+	return run;
+}
+
+// workgroup-wide exclusive prefix maximum of the per-thread maxima (one barrier; wmax: one float per wave)
+__device__ __forceinline__ float aln_excl_prefix_max(float run, float *wmax, u32 lane, u32 wave)
+{
+	const float incl = mpc_wave_scan_max_nonneg(run);
+	float excl = mpc_lane_up1(incl);
+	if (lane == 0) excl = 0.0f;
+	if (lane == 63) wmax[wave] = incl;
+	__syncthreads();
+	for (u32 w = 0; w < wave; ++w) { const float o = wmax[w]; excl = o >= excl ? o : excl; }
+	return excl;
+}
+
+// pass 2: S and the traceback letters of my columns. Y: S(i, a + l0 - 1) in, S(i, a + l1 - 1) out
+__device__ __forceinline__ float aln_lds_pass2(const float *oldr, float *newr, const float *prow, char *tbrow, u32 a, u32 l0, u32 l1, u32 slot, float Y)
+{
+	for (u32 l = l0; l < l1; ++l) {
+		const u32 j = a + l;
+		if (j == 0) { newr[slot] = 0.0f; tbrow[0] = 'X'; Y = 0.0f; continue; } // calcalnflat.cpp:23-25
+		const float B = oldr[l + slot - 1] + prow[j - 1];
+		const float X = oldr[l + slot];
+		const bool bx = B >= X;            // best3.h:9
+		const float T = bx ? B : X;
+		const bool ty = T >= Y;            // best3.h:11 / :21
+		const float S = ty ? T : Y;
+		newr[l + slot] = S;
+		tbrow[j] = ty ? (bx ? 'B' : 'X') : 'Y';
+		Y = S;
+	}
+	return Y;
+}
+
+// the path, reversed by the whole workgroup (stride: its size)
+__device__ __forceinline__ void aln_reverse_path(const AlnParams &p, u32 n, u32 tid, u32 stride)
+{
+	for (u32 k = tid; k < n; k += stride) p.path[k] = p.rev[n - 1 - k];
+}
+
+// TraceBackFlat (tracebackflat.cpp:3-37) over the 'B' / 'X' / 'Y' bytes in device memory: one lane walks, the length goes through LDS (s_n),
+// the workgroup reverses. score: where thread 0 finds S(LX, LY)
+__device__ __forceinline__ void aln_walk_back_bytes(const AlnParams &p, const float *score, u32 *s_n, u32 tid)
+{
+	const u32 W = p.LY + 1;
+	if (tid == 0) {
+		*p.score = *score;
+		int i = (int)p.LX, j = (int)p.LY;
+		u32 n = 0;
+		while (i != 0 || j != 0) {
+			const char c = p.tb[(u64)i * W + j];
+			p.rev[n++] = c;
+			if (c == 'B') { --i; --j; } else if (c == 'X') --i; else --j;
+		}
+		*s_n = n;
+		*p.pathlen = n;
+	}
+	__syncthreads();
+	aln_reverse_path(p, *s_n, tid, MPC_ALN_THREADS);
+}
+
 __global__ void __launch_bounds__(MPC_ALN_THREADS) calc_aln_kernel(AlnParams p)
 {
 	MPC_DYN_SMEM(smem_raw);
@@ -45,55 +118,13 @@ __global__ void __launch_bounds__(MPC_ALN_THREADS) calc_aln_kernel(AlnParams p)
 	__syncthreads();
 	for (u32 i = 1; i <= LX; ++i) {
 		const float *prow = p.post + (u64)(i - 1) * LY;
-		char *tbrow = p.tb + (u64)i * W;
-		// pass 1: maximum of T over my columns
-		float run = 0.0f; // T_j >= 0 always (X >= 0), and S(i,0) = 0
-		for (u32 j = (j0 == 0 ? 1u : j0); j < j1; ++j) {
-			const float B = oldr[j - 1] + prow[j - 1];
-			const float X = oldr[j];
-			const float T = B >= X ? B : X;
-			run = T >= run ? T : run;
-		}
-		// workgroup-wide exclusive prefix maximum of the per-thread maxima
-		const float incl = mpc_wave_scan_max_nonneg(run);
-		float excl = mpc_lane_up1(incl);
-		if (lane == 0) excl = 0.0f;
-		if (lane == 63) wmax[wave] = incl;
-		__syncthreads();
-		for (u32 w = 0; w < wave; ++w) { const float o = wmax[w]; excl = o >= excl ? o : excl; }
-		// pass 2: S and the traceback letters
-		float Y = excl; // S(i, j0-1)
-		for (u32 j = j0; j < j1; ++j) {
-			if (j == 0) { newr[0] = 0.0f; tbrow[0] = 'X'; Y = 0.0f; continue; } // calcalnflat.cpp:23-25
-			const float B = oldr[j - 1] + prow[j - 1];
-			const float X = oldr[j];
-			const bool bx = B >= X;            // best3.h:9
-			const float T = bx ? B : X;
-			const bool ty = T >= Y;            // best3.h:11 / :21
-			const float S = ty ? T : Y;
-			newr[j] = S;
-			tbrow[j] = ty ? (bx ? 'B' : 'X') : 'Y';
-			Y = S;
-		}
+		const float run = aln_lds_pass1(oldr, prow, 0, j0, j1, 0);
+		const float excl = aln_excl_prefix_max(run, wmax, lane, wave); // S(i, j0-1)
+		aln_lds_pass2(oldr, newr, prow, p.tb + (u64)i * W, 0, j0, j1, 0, excl);
 		__syncthreads();
 		float *tmp = oldr; oldr = newr; newr = tmp;
 	}
-	// TraceBackFlat (tracebackflat.cpp:3-37)
-	if (tid == 0) {
-		*p.score = oldr[LY];
-		int i = (int)LX, j = (int)LY;
-		u32 n = 0;
-		while (i != 0 || j != 0) {
-			const char c = p.tb[(u64)i * W + j];
-			p.rev[n++] = c;
-			if (c == 'B') { --i; --j; } else if (c == 'X') --i; else --j;
-		}
-		*s_n = n;
-		*p.pathlen = n;
-	}
-	__syncthreads();
-	const u32 n = *s_n;
-	for (u32 k = tid; k < n; k += MPC_ALN_THREADS) p.path[k] = p.rev[n - 1 - k];
+	aln_walk_back_bytes(p, &oldr[LY], s_n, tid);
 }
 
 // ---- one wavefront per alignment (the common size: both alignments <= 512 columns, <= 600 rows) -----------------------
@@ -111,6 +142,67 @@ __global__ void __launch_bounds__(MPC_ALN_THREADS) calc_aln_kernel(AlnParams p)
 #define MPC_ALNW_PF 4                      // rows of Post in flight
 #endif
 
+// ---- the prefetch ring of the register-row kernels (wave, quad)
+// Post(i-1, j-1) of my columns, PF rows ahead: the row loop is a dependent chain of ~0.2 us per row and a load from
+// HBM/L2 takes ~1-2 us, so one row of lookahead leaves the chain waiting on memory every row (measured: 1.5 us per row).
+// The loads are unconditional (a branch around a load makes the compiler wait for ALL loads in flight, vmcnt(0), at the
+// next use): rows past LX and columns outside 1..LY read a clamped in-range address instead, and what they read is never
+// used (column 0 and the columns past LY get their S and letter without it and stay out of the row maximum).
+template <int C, int PF>
+struct AlnPostRing {
+	float ring[PF][C];
+	u32 coff[C]; // clamped column offsets: the same for every row
+	__device__ __forceinline__ void load_row(const AlnParams &p, float *dst, u32 i) const
+	{
+		const float *prow = p.post + (u64)((i <= p.LX ? i : p.LX) - 1u) * p.LY;
+#pragma unroll
+		for (int c = 0; c < C; ++c) dst[c] = prow[coff[c]];
+	}
+	__device__ __forceinline__ void prime(const AlnParams &p, u32 j0)
+	{
+#pragma unroll
+		for (int c = 0; c < C; ++c) {
+			const u32 j = j0 + c;
+			coff[c] = (j < 1u ? 1u : (j > p.LY ? p.LY : j)) - 1u;
+		}
+#pragma unroll
+		for (int r = 0; r < PF; ++r) { load_row(p, ring[r], 1u + r); MPC_SCHED_BARRIER(); } // issued oldest row first: the waits count loads in order
+	}
+	// row i out of slot r = (i - 1) % PF, row i + PF into it
+	__device__ __forceinline__ void take(const AlnParams &p, int r, u32 i, float (&pvc)[C])
+	{
+#pragma unroll
+		for (int c = 0; c < C; ++c) pvc[c] = ring[r][c];
+		load_row(p, ring[r], i + PF);
+		MPC_SCHED_BARRIER();
+	}
+};
+
+// ---- the cell code of the register-row kernels (wave, quad), once: column j of row i, oldr = S(i-1, .)
+// opens the cell: B = diag + Post, bx = B >= X, T = max(B, X) (the caller takes T into the row's maximum when the column is inside 1..LY)
+struct AlnCell { float v; bool bx; u32 code; }; // T, bx (code: not used; the listing that was timed has it, and without it the compares come out swapped)
+__device__ __forceinline__ AlnCell aln_cell_open(float diag, float post, float X)
+{
+	AlnCell r;
+	const float B = diag + post;
+	r.bx = B >= X; // best3.h:9
+	r.v = r.bx ? B : X;
+	return r;
+}
+// closes it with Y = S(i, j-1): returns S(i, j) and the cell's code (0 = 'B', 1 = 'X', 2 = 'Y')
+__device__ __forceinline__ float aln_cell_close(float T, bool bx, float Y, u32 j, u32 LY, u32 &code)
+{
+	float S;
+	if (j == 0) { S = 0.0f; code = 1u; } // calcalnflat.cpp:23-25: column 0 = 'X'
+	else {
+		const bool ty = T >= Y; // best3.h:11 / :21
+		S = ty ? T : Y;
+		code = ty ? (bx ? 0u : 1u) : 2u;
+	}
+	if (j > LY) { S = 0.0f; code = 2u; } // beyond the matrix: never read
+	return S;
+}
+
 template <int C> // columns per lane: 64 * C >= LY + 1
 __device__ __forceinline__ void calc_aln_wave_body_c(const AlnParams &p, unsigned char *smem_raw) // smem_raw: (LX+1) rows of MPC_ALNW_ROWBYTES traceback nibbles
 {
@@ -122,35 +214,15 @@ __device__ __forceinline__ void calc_aln_wave_body_c(const AlnParams &p, unsigne
 #pragma unroll
 	for (int c = 0; c < C; ++c) { oldr[c] = 0.0f; code0 |= 2u << (4 * c); }
 	((u32 *)smem_raw)[lane] = code0;
-	// Post(i-1, j-1) of my columns, MPC_ALNW_PF rows ahead: the row loop is a dependent chain of ~0.2 us per row and a load from
-	// HBM/L2 takes ~1-2 us, so one row of lookahead leaves the chain waiting on memory every row (measured: 1.5 us per row).
-	// The loads are unconditional (a branch around a load makes the compiler wait for ALL loads in flight, vmcnt(0), at the
-	// next use): rows past LX and columns outside 1..LY read a clamped in-range address instead, and what they read is never
-	// used (column 0 and the columns past LY get their S and letter without it and stay out of the row maximum).
-	float ring[MPC_ALNW_PF][C];
-	u32 coff[C]; // clamped column offsets: the same for every row
-#pragma unroll
-	for (int c = 0; c < C; ++c) {
-		const u32 j = j0 + c;
-		coff[c] = (j < 1u ? 1u : (j > LY ? LY : j)) - 1u;
-	}
-	auto load_row = [&](float *dst, u32 i) {
-		const float *prow = p.post + (u64)((i <= LX ? i : LX) - 1u) * LY;
-#pragma unroll
-		for (int c = 0; c < C; ++c) dst[c] = prow[coff[c]];
-	};
-#pragma unroll
-	for (int r = 0; r < MPC_ALNW_PF; ++r) { load_row(ring[r], 1u + r); MPC_SCHED_BARRIER(); } // issued oldest row first: the waits count loads in order
+	AlnPostRing<C, MPC_ALNW_PF> ring;
+	ring.prime(p, j0);
 	for (u32 ib = 1; ib <= LX; ib += MPC_ALNW_PF) {
 #pragma unroll
 	for (int r = 0; r < MPC_ALNW_PF; ++r) {
 		const u32 i = ib + r;
 		if (i > LX) break; // wave-uniform
 		float pvc[C];
-#pragma unroll
-		for (int c = 0; c < C; ++c) pvc[c] = ring[r][c];
-		load_row(ring[r], i + MPC_ALNW_PF);
-		MPC_SCHED_BARRIER();
+		ring.take(p, r, i, pvc);
 		// S(i-1, j0-1): the previous lane's last column of the previous row
 		float left_old = mpc_lane_up1(oldr[C - 1]);
 		if (lane == 0) left_old = 0.0f; // unused (column 0 has no B)
@@ -160,11 +232,8 @@ __device__ __forceinline__ void calc_aln_wave_body_c(const AlnParams &p, unsigne
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			const u32 j = j0 + c;
-			const float diag = c == 0 ? left_old : oldr[c - 1];
-			const float B = diag + pvc[c];
-			const float X = oldr[c];
-			bx[c] = B >= X; // best3.h:9
-			T[c] = bx[c] ? B : X;
+			const AlnCell o = aln_cell_open(c == 0 ? left_old : oldr[c - 1], pvc[c], oldr[c]);
+			bx[c] = o.bx; T[c] = o.v;
 			if (j >= 1 && j <= LY) run = T[c] >= run ? T[c] : run;
 		}
 		// exclusive prefix maximum over the lanes = S(i, j0-1)
@@ -174,16 +243,8 @@ __device__ __forceinline__ void calc_aln_wave_body_c(const AlnParams &p, unsigne
 		u32 codes = 0;
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
-			const u32 j = j0 + c;
-			float S;
 			u32 code;
-			if (j == 0) { S = 0.0f; code = 1u; } // calcalnflat.cpp:23-25: column 0 = 'X'
-			else {
-				const bool ty = T[c] >= Y; // best3.h:11 / :21
-				S = ty ? T[c] : Y;
-				code = ty ? (bx[c] ? 0u : 1u) : 2u;
-			}
-			if (j > LY) { S = 0.0f; code = 2u; } // beyond the matrix: never read
+			const float S = aln_cell_close(T[c], bx[c], Y, j0 + c, LY, code);
 			oldr[c] = S;
 			codes |= code << (4 * c);
 			Y = S;
@@ -215,8 +276,7 @@ __device__ __forceinline__ void calc_aln_wave_body_c(const AlnParams &p, unsigne
 		*p.pathlen = n;
 	}
 	__syncthreads();
-	const u32 n = *s_n;
-	for (u32 k = lane; k < n; k += 64) p.path[k] = p.rev[n - 1 - k];
+	aln_reverse_path(p, *s_n, lane, 64);
 	(void)W;
 }
 
@@ -263,19 +323,20 @@ struct DensePostParams {
 	float *out;
 };
 
-__global__ void __launch_bounds__(256) dense_post_kernel(DensePostParams p)
+// zero, then scatter pair q's list into the matrix at out_off[s] (read behind the early-out, where the kernels always read it)
+__device__ __forceinline__ void dense_post_scatter(const DensePostParams &p, u32 q, u32 s)
 {
-	const u32 q = blockIdx.x;
 	const u32 LX = p.seq_len[p.pair_x[q]], LY = p.seq_len[p.pair_y[q]];
 	const u32 c = p.cand_cnt[q];
 	// an overflowed list (the short path of mpcgpu_align_pairs launches this before the host sees the flag) holds only its first
-	// capc entries; the count runs past its slot and the buffer. The host drops this matrix and redoes the pair.
+	// capc entries; the count runs past its slot and the buffer. The host drops this matrix and redoes the pair (mpcgpu_search_pairs:
+	// drops the chunk and redoes it).
 	if (c > p.capc) return;
-	float *M = p.out + p.out_off[q];
+	float *M = p.out + p.out_off[s];
 	const u64 cells = (u64)LX * LY;
 	for (u64 e = threadIdx.x; e < cells; e += blockDim.x) M[e] = 0.0f;
 	__syncthreads();
-	const u32 kshift = LX >= p.long_min ? MPC_KEY_ROW_SHIFT_LONG : MPC_KEY_ROW_SHIFT;
+	const u32 kshift = mpc_key_shift(LX, p.long_min);
 	const u64 *cand = p.cand + (u64)q * p.capc;
 	for (u32 e = threadIdx.x; e < c; e += blockDim.x) {
 		const u64 v = cand[e];
@@ -283,6 +344,12 @@ __global__ void __launch_bounds__(256) dense_post_kernel(DensePostParams p)
 		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
 		M[(u64)row * LY + col] = __uint_as_float((u32)v);
 	}
+}
+
+__global__ void __launch_bounds__(256) dense_post_kernel(DensePostParams p)
+{
+	const u32 q = blockIdx.x;
+	dense_post_scatter(p, q, q);
 }
 
 // The same matrix from the RAW candidate lists the sort-based post_kernel leaves behind (kernels_post.h: it copies (key, score
@@ -297,30 +364,36 @@ struct DensePostRawParams {
 	u32 slabs; // workgroups per pair: workgroup b serves slab b % slabs of pair b / slabs
 };
 
-__global__ void __launch_bounds__(256) dense_post_raw_kernel(DensePostRawParams p)
+// slab `slab` of `slabs` of pair q's raw list into the (zeroed) matrix at out_off[s]
+__device__ __forceinline__ void dense_post_raw_scatter(const DensePostParams &p, u32 q, u32 s, u32 slab, u32 slabs, int use_fma)
 {
-	const u32 q = blockIdx.x / p.slabs, slab = blockIdx.x % p.slabs;
-	const u32 LX = p.d.seq_len[p.d.pair_x[q]], LY = p.d.seq_len[p.d.pair_y[q]];
-	const u32 c = p.d.cand_cnt[q];
-	if (c > p.d.capc) return;
-	float *M = p.d.out + p.d.out_off[q];
-	const u32 kshift = mpc_key_shift(LX, p.d.long_min);
-	const u64 *cand = p.d.cand + (u64)q * p.d.capc;
-	for (u32 e = slab * blockDim.x + threadIdx.x; e < c; e += p.slabs * blockDim.x) {
+	const u32 LX = p.seq_len[p.pair_x[q]], LY = p.seq_len[p.pair_y[q]];
+	const u32 c = p.cand_cnt[q];
+	if (c > p.capc) return;
+	float *M = p.out + p.out_off[s];
+	const u32 kshift = mpc_key_shift(LX, p.long_min);
+	const u64 *cand = p.cand + (u64)q * p.capc;
+	for (u32 e = slab * blockDim.x + threadIdx.x; e < c; e += slabs * blockDim.x) {
 		const u64 v = cand[e];
 		const u32 key = (u32)(v >> 32);
 		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
-		const float pr = mpc_score_to_prob(__uint_as_float((u32)v), p.use_fma);
+		const float pr = mpc_score_to_prob(__uint_as_float((u32)v), use_fma);
 		if (row < LX && col < LY) M[(u64)row * LY + col] = pr; // (a key is a cell of the matrix: the test only keeps a damaged list inside it)
 	}
+}
+
+__global__ void __launch_bounds__(256) dense_post_raw_kernel(DensePostRawParams p)
+{
+	const u32 q = blockIdx.x / p.slabs, slab = blockIdx.x % p.slabs;
+	dense_post_raw_scatter(p.d, q, q, slab, p.slabs, p.use_fma);
 }
 
 // ---- the INDIRECT forms (mpcgpu_search_pairs, mpcgpu_search.inc): one workgroup per SLOT, and which pair of the batch a slot serves is
 // read from pick[slot] on the device — MPC_PICK_NONE: the workgroup leaves at once. A slot is a group of candidate pairs of which at most
 // one is kept (uclust.cpp:44-54: the first hit whose EA reaches the threshold), chosen by search_pick_kernel (kernels_search.h) behind the
 // finishing kernel on the same stream: no dense matrix and no trace-back for the others, and nothing read back in between. Slot s's matrix
-// lies at out_off[s], sized by the host for the slot's largest LX x LY. The cell code is dense_post_kernel's, dense_post_raw_kernel's and
-// calc_aln_wave_body: same bits, same letters. The direct kernels above are left as they are (their listings do not move).
+// lies at out_off[s], sized by the host for the slot's largest LX x LY. The cell code is the direct kernels': dense_post_scatter,
+// dense_post_raw_scatter and calc_aln_wave_body.
 #define MPC_PICK_NONE 0xffffffffu
 
 struct DensePostPickParams {
@@ -332,21 +405,7 @@ __global__ void __launch_bounds__(256) dense_post_pick_kernel(DensePostPickParam
 {
 	const u32 q = p.pick[blockIdx.x];
 	if (q == MPC_PICK_NONE) return;
-	const u32 LX = p.d.seq_len[p.d.pair_x[q]], LY = p.d.seq_len[p.d.pair_y[q]];
-	const u32 c = p.d.cand_cnt[q];
-	if (c > p.d.capc) return; // an overflowed list: the host drops the chunk and redoes it (dense_post_kernel)
-	float *M = p.d.out + p.d.out_off[blockIdx.x];
-	const u64 cells = (u64)LX * LY;
-	for (u64 e = threadIdx.x; e < cells; e += blockDim.x) M[e] = 0.0f;
-	__syncthreads();
-	const u32 kshift = LX >= p.d.long_min ? MPC_KEY_ROW_SHIFT_LONG : MPC_KEY_ROW_SHIFT;
-	const u64 *cand = p.d.cand + (u64)q * p.d.capc;
-	for (u32 e = threadIdx.x; e < c; e += blockDim.x) {
-		const u64 v = cand[e];
-		const u32 key = (u32)(v >> 32);
-		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
-		M[(u64)row * LY + col] = __uint_as_float((u32)v);
-	}
+	dense_post_scatter(p.d, q, blockIdx.x);
 }
 
 // ... from the raw candidate lists (dense_post_raw_kernel): the host has zeroed the slots' matrices; workgroup b serves slab b % slabs of slot b / slabs
@@ -360,19 +419,7 @@ __global__ void __launch_bounds__(256) dense_post_raw_pick_kernel(DensePostRawPi
 	const u32 s = blockIdx.x / p.r.slabs, slab = blockIdx.x % p.r.slabs;
 	const u32 q = p.pick[s];
 	if (q == MPC_PICK_NONE) return;
-	const u32 LX = p.r.d.seq_len[p.r.d.pair_x[q]], LY = p.r.d.seq_len[p.r.d.pair_y[q]];
-	const u32 c = p.r.d.cand_cnt[q];
-	if (c > p.r.d.capc) return;
-	float *M = p.r.d.out + p.r.d.out_off[s];
-	const u32 kshift = mpc_key_shift(LX, p.r.d.long_min);
-	const u64 *cand = p.r.d.cand + (u64)q * p.r.d.capc;
-	for (u32 e = slab * blockDim.x + threadIdx.x; e < c; e += p.r.slabs * blockDim.x) {
-		const u64 v = cand[e];
-		const u32 key = (u32)(v >> 32);
-		const u32 row = key >> kshift, col = key & ((1u << kshift) - 1u);
-		const float pr = mpc_score_to_prob(__uint_as_float((u32)v), p.r.use_fma);
-		if (row < LX && col < LY) M[(u64)row * LY + col] = pr;
-	}
+	dense_post_raw_scatter(p.r.d, q, s, slab, p.r.slabs, p.r.use_fma);
 }
 
 // the one-wave alignment of slot s's matrix: the AlnParams record calc_aln_wave_batch_kernel reads from the host is formed here, from the
@@ -429,42 +476,12 @@ __global__ void __launch_bounds__(MPC_ALN_THREADS) calc_aln_tiled_kernel(AlnPara
 		__syncthreads();
 		for (u32 i = 1; i <= LX; ++i) {
 			const float *prow = p.post + (u64)(i - 1) * LY;
-			char *tbrow = p.tb + (u64)i * W;
 			const float left_i = left;
 			left = a ? bin[i < LX ? i + 1 : LX] : 0.0f;
-			// pass 1: maximum of T over my columns
-			float run = 0.0f; // T_j >= 0 always (X >= 0), and S(i,0) = 0
-			for (u32 l = l0; l < l1; ++l) {
-				const u32 j = a + l;
-				if (j == 0) continue;
-				const float B = oldr[l] + prow[j - 1];
-				const float X = oldr[l + 1];
-				const float T = B >= X ? B : X;
-				run = T >= run ? T : run;
-			}
-			// workgroup-wide exclusive prefix maximum of the per-thread maxima, over S(i, a - 1)
-			const float incl = mpc_wave_scan_max_nonneg(run);
-			float excl = mpc_lane_up1(incl);
-			if (lane == 0) excl = 0.0f;
-			if (lane == 63) wmax[wave] = incl;
-			__syncthreads();
-			for (u32 w = 0; w < wave; ++w) { const float o = wmax[w]; excl = o >= excl ? o : excl; }
-			excl = left_i >= excl ? left_i : excl;
-			// pass 2: S and the traceback letters
-			float Y = excl; // S(i, a + l0 - 1)
-			for (u32 l = l0; l < l1; ++l) {
-				const u32 j = a + l;
-				if (j == 0) { newr[1] = 0.0f; tbrow[0] = 'X'; Y = 0.0f; continue; } // calcalnflat.cpp:23-25
-				const float B = oldr[l] + prow[j - 1];
-				const float X = oldr[l + 1];
-				const bool bx = B >= X;            // best3.h:9
-				const float T = bx ? B : X;
-				const bool ty = T >= Y;            // best3.h:11 / :21
-				const float S = ty ? T : Y;
-				newr[l + 1] = S;
-				tbrow[j] = ty ? (bx ? 'B' : 'X') : 'Y';
-				Y = S;
-			}
+			const float run = aln_lds_pass1(oldr, prow, a, l0, l1, 1);
+			float excl = aln_excl_prefix_max(run, wmax, lane, wave);
+			excl = left_i >= excl ? left_i : excl; // ... over S(i, a - 1)
+			const float Y = aln_lds_pass2(oldr, newr, prow, p.tb + (u64)i * W, a, l0, l1, 1, excl);
 			if (l0 < n && l1 == n) { bout[i] = Y; last = Y; } // the tile's last column: the next tile's left edge
 			if (tid == 0) newr[0] = left_i;
 			__syncthreads();
@@ -481,22 +498,7 @@ __global__ void __launch_bounds__(MPC_ALN_THREADS) calc_aln_tiled_kernel(AlnPara
 		if (l0 < n && l1 == n) *s_score = last;
 	}
 	__syncthreads();
-	// TraceBackFlat (tracebackflat.cpp:3-37)
-	if (tid == 0) {
-		*p.score = *s_score;
-		int i = (int)LX, j = (int)LY;
-		u32 n = 0;
-		while (i != 0 || j != 0) {
-			const char c = p.tb[(u64)i * W + j];
-			p.rev[n++] = c;
-			if (c == 'B') { --i; --j; } else if (c == 'X') --i; else --j;
-		}
-		*s_n = n;
-		*p.pathlen = n;
-	}
-	__syncthreads();
-	const u32 n = *s_n;
-	for (u32 k = tid; k < n; k += MPC_ALN_THREADS) p.path[k] = p.rev[n - 1 - k];
+	aln_walk_back_bytes(p, s_score, s_n, tid);
 }
 
 // ---- several wavefronts, previous row in registers (matrices wider than one wave holds: the joins near the root) ---------
@@ -529,41 +531,23 @@ __global__ void __launch_bounds__(1024) calc_aln_quad_kernel(AlnParams p, u32 bl
 	for (int c = 0; c < MPC_ALNQ_C; ++c) oldr[c] = 0.0f;
 	tb[tid] = 0xaau; // row 0: 'Y' everywhere (calcalnflat.cpp:15-19); codes: 0 = 'B', 1 = 'X', 2 = 'Y'
 	float left_old = 0.0f; // S(i-1, j0-1)
-	float ring[MPC_ALNQ_PF][MPC_ALNQ_C];
-	u32 coff[MPC_ALNQ_C]; // clamped column offsets, unconditional loads: see calc_aln_wave_kernel
-#pragma unroll
-	for (int c = 0; c < MPC_ALNQ_C; ++c) {
-		const u32 j = j0 + c;
-		coff[c] = (j < 1u ? 1u : (j > LY ? LY : j)) - 1u;
-	}
-	auto load_row = [&](float *dst, u32 i) {
-		const float *prow = p.post + (u64)((i <= LX ? i : LX) - 1u) * LY;
-#pragma unroll
-		for (int c = 0; c < MPC_ALNQ_C; ++c) dst[c] = prow[coff[c]];
-	};
-#pragma unroll
-	for (int r = 0; r < MPC_ALNQ_PF; ++r) { load_row(ring[r], 1u + r); MPC_SCHED_BARRIER(); } // issued oldest row first: the waits count loads in order
+	AlnPostRing<MPC_ALNQ_C, MPC_ALNQ_PF> ring;
+	ring.prime(p, j0);
 	for (u32 ib = 1; ib <= LX; ib += MPC_ALNQ_PF) {
 #pragma unroll
 	for (int r = 0; r < MPC_ALNQ_PF; ++r) {
 		const u32 i = ib + r;
 		if (i > LX) break; // uniform
 		float pvc[MPC_ALNQ_C];
-#pragma unroll
-		for (int c = 0; c < MPC_ALNQ_C; ++c) pvc[c] = ring[r][c];
-		load_row(ring[r], i + MPC_ALNQ_PF);
-		MPC_SCHED_BARRIER();
+		ring.take(p, r, i, pvc);
 		float T[MPC_ALNQ_C];
 		bool bx[MPC_ALNQ_C];
 		float run = 0.0f; // T_j >= 0 always (X >= 0), and S(i,0) = 0
 #pragma unroll
 		for (int c = 0; c < MPC_ALNQ_C; ++c) {
 			const u32 j = j0 + c;
-			const float diag = c == 0 ? left_old : oldr[c - 1];
-			const float B = diag + pvc[c];
-			const float X = oldr[c];
-			bx[c] = B >= X; // best3.h:9
-			T[c] = bx[c] ? B : X;
+			const AlnCell o = aln_cell_open(c == 0 ? left_old : oldr[c - 1], pvc[c], oldr[c]);
+			bx[c] = o.bx; T[c] = o.v;
 			if (j >= 1 && j <= LY) run = T[c] >= run ? T[c] : run;
 		}
 		const float incl = mpc_wave_scan_max_nonneg(run);
@@ -577,16 +561,8 @@ __global__ void __launch_bounds__(1024) calc_aln_quad_kernel(AlnParams p, u32 bl
 		u32 codes = 0;
 #pragma unroll
 		for (int c = 0; c < MPC_ALNQ_C; ++c) {
-			const u32 j = j0 + c;
-			float S;
 			u32 code;
-			if (j == 0) { S = 0.0f; code = 1u; } // calcalnflat.cpp:23-25: column 0 = 'X'
-			else {
-				const bool ty = T[c] >= Y; // best3.h:11 / :21
-				S = ty ? T[c] : Y;
-				code = ty ? (bx[c] ? 0u : 1u) : 2u;
-			}
-			if (j > LY) { S = 0.0f; code = 2u; } // beyond the matrix: never read
+			const float S = aln_cell_close(T[c], bx[c], Y, j0 + c, LY, code);
 			oldr[c] = S;
 			codes |= code << (2 * c);
 			Y = S;
@@ -628,5 +604,5 @@ __global__ void __launch_bounds__(1024) calc_aln_quad_kernel(AlnParams p, u32 bl
 	}
 	const u32 n = s_state[2];
 	if (tid == 0) *p.pathlen = n;
-	for (u32 k = tid; k < n; k += blockDim.x) p.path[k] = p.rev[n - 1 - k];
+	aln_reverse_path(p, n, tid, blockDim.x);
 }

@@ -181,7 +181,7 @@ struct mpcgpu_ctx {
 	u64 total_entries = 0;
 	u32 max_nnz = 0, max_len = 0;
 	HostBuf h_bp_in, h_aln_res;
-	size_t aln_smem_set[5] = {0, 0, 0, 0, 0}; // largest dynamic LDS each CalcAlnFlat kernel has been allowed so far
+	size_t aln_smem_set[6] = {0, 0, 0, 0, 0, 0}; // largest dynamic LDS each CalcAlnFlat kernel has been allowed so far (aln_smem_raise)
 	DevBuf d_tile_next, d_bp_in, d_aln_res, d_bp_seq, d_bp_map, d_bp_off, d_bp_coff, d_bp_keys, d_bp_vals, d_bp_tmp, d_bp_runs;
 	DevBuf d_tiles, d_pad, d_pos, d_aln_post, d_aln_tb, d_aln_rev, d_aln_bnd;
 	bool have_pad = false;       // variable-size dense records + relax_var_kernel (else: slabs + gather relax)
@@ -312,14 +312,12 @@ struct mpcgpu_ctx {
 		float smin = 0, smax = 0;
 	} up;
 	// mpcgpu_search_pairs (mpcgpu_search.inc): the page-locked record of a chunk and its device copy, sizes / EA / flags of the chunk's pairs as the
-	// finishing kernel leaves them, the picks of the general route, the events around pick + dense + alignment, the largest dynamic LDS
-	// calc_aln_wave_pick_kernel has been allowed; last: the last list stage was a search (mpcgpu_get_list_sparse refuses); and what
-	// mpcgpu_search_info reports of the last call
+	// finishing kernel leaves them, the picks of the general route, the events around pick + dense + alignment; last: the last list
+	// stage was a search (mpcgpu_get_list_sparse refuses); and what mpcgpu_search_info reports of the last call
 	struct SearchState {
 		HostBuf h;
-		DevBuf d_in, d_nnz, d_ea, d_flags, d_pick, d_off;
+		DevBuf d_in, d_nnz, d_ea, d_flags, d_pick;
 		hipEvent_t ev0 = nullptr, ev1 = nullptr;
-		size_t aln_smem = 0;
 		bool last = false;
 		u64 groups = 0, pairs = 0, traced = 0, chunks = 0, general = 0;
 		double ms = 0;
@@ -786,7 +784,7 @@ void mpcgpu_destroy(mpcgpu_ctx *c)
 	c->ea.d_wkeys.release(); c->ea.d_wrs.release(); c->ea.d_wsrow.release(); c->ea.d_winfo.release();
 	if (c->ea.ev) (void)hipEventDestroy(c->ea.ev);
 	c->se.h.release();
-	for (DevBuf *b : {&c->se.d_in, &c->se.d_nnz, &c->se.d_ea, &c->se.d_flags, &c->se.d_pick, &c->se.d_off}) b->release();
+	for (DevBuf *b : {&c->se.d_in, &c->se.d_nnz, &c->se.d_ea, &c->se.d_flags, &c->se.d_pick}) b->release();
 	if (c->se.ev0) (void)hipEventDestroy(c->se.ev0);
 	if (c->se.ev1) (void)hipEventDestroy(c->se.ev1);
 	c->pad_seg.release(); release_windows(c);

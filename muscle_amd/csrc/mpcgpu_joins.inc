@@ -9,6 +9,14 @@ static const u64 MPC_ROWS_CELLS1_MAX_BATCH = 1u << 22; // the same in a list of 
 // the one-wave alignment (calc_aln_wave_kernel and its batch form): LY + 1 columns in a wave's registers, LX + 1 rows of traceback codes in LDS
 static size_t aln_wave_smem(u64 lds_rows) { return (size_t)(lds_rows * MPC_ALNW_ROWBYTES + 16); }
 static bool aln_wave_fits(u32 LX, u32 LY) { return (u64)LY + 1 <= MPC_ALNW_MAXW && aln_wave_smem((u64)LX + 1) <= MPC_LDS_MAX; }
+// raise a CalcAlnFlat kernel's dynamic-LDS limit only when this call needs more than any before; which: the kernel's entry of aln_smem_set
+// (0 one wave, 1 several waves, 2 LDS rows, 3 one wave per alignment of a batch, 4 column tiles, 5 one wave per picked slot)
+static void aln_smem_raise(mpcgpu_ctx *c, int which, const void *kernel, size_t smem)
+{
+	if (smem <= c->aln_smem_set[which]) return;
+	(void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+	c->aln_smem_set[which] = smem;
+}
 
 // ---- the result record of an alignment {u32 path length, f32 score, path of at most LX + LY letters}: written by the kernel, read by the host
 static u64 aln_rec_stride(u64 Lsum) { return (8 + Lsum + 7) & ~7ull; } // from one record to the next where several lie together
@@ -48,12 +56,8 @@ static int run_calc_aln(mpcgpu_ctx *c, const float *d_post, uint32_t LX, uint32_
 	HIPCHK(c, c->h_aln_res.ensure(8 + (u64)LX + LY)); // one result record, unpadded
 	// the record is written straight into page-locked host memory (device-visible: hipHostMalloc): no copy back, one wait
 	const AlnParams ap = aln_params(d_post, LX, LY, c->d_aln_tb.as<char>(), c->d_aln_rev.as<char>(), c->h_aln_res.as<char>());
-	const int which = wave ? 0 : quad ? 1 : tiled ? 4 : 2;
-	if (smem > c->aln_smem_set[which]) { // raise the kernel's dynamic-LDS limit only when this call needs more than any before
-		(void)hipFuncSetAttribute(wave ? (const void *)calc_aln_wave_kernel : quad ? (const void *)calc_aln_quad_kernel : tiled ? (const void *)calc_aln_tiled_kernel : (const void *)calc_aln_kernel,
-			hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-		c->aln_smem_set[which] = smem;
-	}
+	aln_smem_raise(c, wave ? 0 : quad ? 1 : tiled ? 4 : 2,
+		wave ? (const void *)calc_aln_wave_kernel : quad ? (const void *)calc_aln_quad_kernel : tiled ? (const void *)calc_aln_tiled_kernel : (const void *)calc_aln_kernel, smem);
 	if (trace_on()) { fprintf(stderr, "[mpcgpu] calc_aln %u x %u: %s\n", LX, LY, wave ? "one wave" : quad ? "waves, rows in registers" : tiled ? "rows in LDS, column tiles" : "rows in LDS"); fflush(stderr); }
 	TimedSpan ts_aln;
 	if (span_begin(c, 8, &ts_aln)) return 1;
@@ -431,10 +435,7 @@ int mpcgpu_align_alns_w(mpcgpu_ctx *c, uint32_t n1, const uint32_t *seq1, uint32
 static int launch_aln_wave_batch(mpcgpu_ctx *c, const AlnParams *ap, u32 n, u32 lds_rows)
 {
 	const size_t smem = aln_wave_smem(lds_rows);
-	if (smem > c->aln_smem_set[3]) {
-		(void)hipFuncSetAttribute((const void *)calc_aln_wave_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-		c->aln_smem_set[3] = smem;
-	}
+	aln_smem_raise(c, 3, (const void *)calc_aln_wave_batch_kernel, smem);
 	TimedSpan ts;
 	if (span_begin(c, 8, &ts)) return 1;
 	MPC_LAUNCH(calc_aln_wave_batch_kernel, n, 64, smem, c->stream, ap);
@@ -669,6 +670,46 @@ static int align_wave_batch(mpcgpu_ctx *c, u32 n, const u32 *sx, const u32 *sy, 
 	return 0;
 }
 
+// ---- the front half of the short-list route, shared by align_pairs_small and search_chunk_fused (mpcgpu_search.inc)
+// what the route asks of a list: no row-block pair, every alignment a one-wave alignment, the row-list finishing kernel. Lsum_max: the longest LX + LY
+static bool short_list_fits(mpcgpu_ctx *c, const StageAGeom &g, u32 np, const u32 *px, const u32 *py, u32 *Lsum_max)
+{
+	if (g.LXlong) return false; // row-block pairs
+	for (u32 q = 0; q < np; ++q) {
+		const u32 LX = c->len[px[q]], LY = c->len[py[q]];
+		if (!aln_wave_fits(LX, LY)) return false; // not a one-wave alignment
+		*Lsum_max = std::max(*Lsum_max, LX + LY);
+	}
+	return post_rows_fits(g.LXmax, g.LYmax, 1024);
+}
+// the context now holds a list stage on these pairs, with nothing packed
+static void short_list_mark(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py)
+{
+	c->have_shard = c->have_store = false;
+	c->shard_is_list = true;
+	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np);
+	c->list_q0 = 0; c->ap_x.clear(); c->ap_y.clear();
+	c->sh_k0 = 0; c->sh_k1 = np;
+}
+// the launch order by rows-per-lane bin H: order[np], and hcount[H] = pairs of bin H
+static void short_list_order(mpcgpu_ctx *c, u32 np, const u32 *px, u32 *order, u32 *hcount)
+{
+	std::fill(hcount, hcount + MPC_HMAX + 1, 0u);
+	std::vector<u32> keys(np);
+	for (u32 q = 0; q < np; ++q) { const u32 H = (c->len[px[q]] + 63) / 64; hcount[H]++; keys[q] = (H << 16) | q; }
+	std::sort(keys.begin(), keys.end());
+	for (u32 q = 0; q < np; ++q) order[q] = keys[q] & 0xffffu;
+}
+// forward / backward, one launch per rows-per-lane bin; then probabilities, EA, sparsify (the candidate lists keep the probabilities): a
+// workgroup per pair, the knobs of the general stage ignored. io, order: as the device reads them
+static int short_list_sweeps(mpcgpu_ctx *c, const StageAGeom &g, const PostIO &io, const u32 *order, const u32 *hcount)
+{
+	FbParams fp;
+	fill_fb_params(c, fp, io.pair_x, io.pair_y, g.capc, g.mega);
+	if (launch_fb_bins(c, g, fp, order, hcount, 0)) return 1;
+	return launch_post_rows(c, g, io, 1024, 64, io.count, c->d_sort_scratch, true);
+}
+
 // mpcgpu_align_pairs for a SHORT list (what UClust::Search and single AlignPairFlat calls send: 1..8 pairs): the kernels of the
 // general path, driven with one wait. Everything the kernels read from the host (pair list, launch order, alignment parameters)
 // and everything the host reads back (candidate-overflow flags, path records) lives in ONE page-locked record that the device
@@ -678,19 +719,10 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 	float *scores, float *ea)
 {
 	const StageAGeom g = stage_a_geom(c, np, px, py);
-	if (g.LXlong) return 2; // row-block pairs: general path
 	u32 Lsum_max = 0;
-	for (u32 q = 0; q < np; ++q) {
-		const u32 LX = c->len[px[q]], LY = c->len[py[q]];
-		if (!aln_wave_fits(LX, LY)) return 2; // not a one-wave alignment
-		Lsum_max = std::max(Lsum_max, LX + LY);
-	}
-	if (!post_rows_fits(g.LXmax, g.LYmax, 1024)) return 2;
-	c->have_shard = c->have_store = false;
-	c->shard_is_list = true; c->se.last = false;
-	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np);
-	c->list_q0 = 0; c->ap_x.clear(); c->ap_y.clear();
-	c->sh_k0 = 0; c->sh_k1 = np;
+	if (!short_list_fits(c, g, np, px, py, &Lsum_max)) return 2;
+	short_list_mark(c, np, px, py);
+	c->se.last = false;
 	// ---- the page-locked record
 	std::vector<u64> off(np + 1, 0);
 	for (u32 q = 0; q < np; ++q) off[q + 1] = off[q] + (u64)c->len[px[q]] * c->len[py[q]];
@@ -703,22 +735,15 @@ static int align_pairs_small(mpcgpu_ctx *c, u32 np, const u32 *px, const u32 *py
 	memcpy(bx, px, 4 * (size_t)np);
 	memcpy(by, py, 4 * (size_t)np);
 	memcpy(h + o_off, off.data(), 8 * ((size_t)np + 1));
-	u32 hcount[MPC_HMAX + 1] = {0};
-	std::vector<u32> keys(np);
-	for (u32 q = 0; q < np; ++q) { const u32 H = (c->len[px[q]] + 63) / 64; hcount[H]++; keys[q] = (H << 16) | q; }
-	std::sort(keys.begin(), keys.end());
-	for (u32 q = 0; q < np; ++q) order[q] = keys[q] & 0xffffu;
+	u32 hcount[MPC_HMAX + 1];
+	short_list_order(c, np, px, order, hcount);
 	// ---- scratch
 	if (ensure_pair_scratch(c, g, np)) return 1;
 	HIPCHK(c, c->d_aln_post.ensure_grow(off[np] * 4));
 	HIPCHK(c, c->d_aln_rev.ensure_grow((u64)np * Lsum_max + 16));
-	// ---- forward / backward, one launch per rows-per-lane bin
-	FbParams fp;
-	fill_fb_params(c, fp, bx, by, g.capc, g.mega);
-	if (launch_fb_bins(c, g, fp, order, hcount, 0)) return 1;
-	// ---- probabilities, EA, sparsify (the candidate lists keep the probabilities): a workgroup per pair, the knobs of the general stage ignored
+	// ---- sweeps and finishing kernel: sizes, EAs and flags straight into the record
 	const PostIO io = {bx, by, c->d_seq_len.as<u32>(), c->d_cand.as<u64>(), c->d_cand_cnt.as<u32>(), c->d_res.as<u32>(), (u32 *)(h + o_nnz), (float *)(h + o_ea), (u32 *)(h + o_flags), np};
-	if (launch_post_rows(c, g, io, 1024, 64, np, c->d_sort_scratch, true)) return 1;
+	if (short_list_sweeps(c, g, io, order, hcount)) return 1;
 	// ---- dense thresholded posteriors, alignments
 	DensePostParams dp;
 	dp.pair_x = bx; dp.pair_y = by; dp.seq_len = c->d_seq_len.as<u32>();
@@ -747,34 +772,36 @@ static int pairs_that_fit(mpcgpu_ctx *c, const u32 *sx, const u32 *sy, u32 *nq)
 }
 
 // The dense thresholded posteriors of the nq pairs of the stage-A batch just run, pair q at off[q] of d_aln_post, rebuilt from the
-// candidate lists the batch left behind (every cell with Score >= MIN_SPARSE_SCORE, also those FromPost drops)
-static int dense_posts(mpcgpu_ctx *c, u32 nq, const std::vector<u64> &off)
+// candidate lists the batch left behind (every cell with Score >= MIN_SPARSE_SCORE, also those FromPost drops). d_pick (mpcgpu_search_pairs):
+// matrix q is that of pair d_pick[q] of the batch, read on the device; NULL: of pair q. refusal: the entry point's words under MPCGPU_POST=sort
+static int dense_posts(mpcgpu_ctx *c, const char *refusal, u32 nq, const std::vector<u64> &off, const u32 *d_pick)
 {
 	// Without the row-list finishing kernel the candidate lists still hold the scores (post_kernel sorts a copy): the raw builder forms
 	// the probabilities itself. Only a list that does not FIT the row-list kernel goes that way; MPCGPU_POST=sort stays a refusal.
 	const char *post_mode = getenv("MPCGPU_POST");
-	if (!c->sa_post_rows && post_mode && !strcmp(post_mode, "sort"))
-		return fail(c, "mpcgpu_align_pairs: pair list with a sequence of more than ~12 000 residues (or MPCGPU_POST=sort): the row-list finishing kernel "
-			"whose candidate lists this entry point rebuilds the dense posteriors from does not take them");
+	if (!c->sa_post_rows && post_mode && !strcmp(post_mode, "sort")) return fail(c, "%s", refusal);
 	HIPCHK(c, c->d_aln_post.ensure_grow(off[nq] * 4));
 	if (upload(c, c->d_ap_off, off)) return 1;
 	DensePostParams dp;
 	dp.pair_x = c->d_bx.as<u32>(); dp.pair_y = c->d_by.as<u32>(); dp.seq_len = c->d_seq_len.as<u32>();
 	dp.cand = c->d_cand.as<u64>(); dp.capc = c->sa_capc; dp.cand_cnt = c->d_cand_cnt.as<u32>(); dp.long_min = c->sa_long_min;
 	dp.out_off = c->d_ap_off.as<u64>(); dp.out = c->d_aln_post.as<float>();
-	if (c->sa_post_rows) MPC_LAUNCH(dense_post_kernel, nq, 256, 0, c->stream, dp);
-	else {
+	if (c->sa_post_rows) {
+		if (d_pick) MPC_LAUNCH(dense_post_pick_kernel, nq, 256, 0, c->stream, DensePostPickParams{dp, d_pick});
+		else MPC_LAUNCH(dense_post_kernel, nq, 256, 0, c->stream, dp);
+	} else {
 		// zeroes by one memset on the stream, the scatter on (pairs) x (slabs of 256 candidates, as many as keep the chip busy)
-		DensePostRawParams rp;
-		rp.d = dp; rp.use_fma = c->use_fma;
-		rp.slabs = (u32)std::max<u64>(1, std::min<u64>(((u64)c->sa_capc + 255) / 256, ((u64)c->prop.multiProcessorCount * 8 + nq - 1) / nq));
-		if (trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs dense posteriors from raw candidates: %u pairs x %u slabs, %.1f MB\n", nq, rp.slabs, (double)off[nq] * 4 / 1048576.0); fflush(stderr); }
+		const u32 slabs = (u32)std::max<u64>(1, std::min<u64>(((u64)c->sa_capc + 255) / 256, ((u64)c->prop.multiProcessorCount * 8 + nq - 1) / nq));
+		const DensePostRawParams rp = {dp, c->use_fma, slabs};
+		// (the trace line and the timed span are mpcgpu_align_pairs' alone: mpcgpu_search_pairs counts no launch in slot 5)
+		if (!d_pick && trace_on()) { fprintf(stderr, "[mpcgpu] align_pairs dense posteriors from raw candidates: %u pairs x %u slabs, %.1f MB\n", nq, slabs, (double)off[nq] * 4 / 1048576.0); fflush(stderr); }
 		TimedSpan ts_dense;
-		if (span_begin(c, 5, &ts_dense)) return 1;
+		if (!d_pick && span_begin(c, 5, &ts_dense)) return 1;
 		HIPCHK(c, hipMemsetAsync(c->d_aln_post.p, 0, off[nq] * 4, c->stream));
-		MPC_LAUNCH(dense_post_raw_kernel, nq * rp.slabs, 256, 0, c->stream, rp);
+		if (d_pick) MPC_LAUNCH(dense_post_raw_pick_kernel, nq * slabs, 256, 0, c->stream, DensePostRawPickParams{rp, d_pick});
+		else MPC_LAUNCH(dense_post_raw_kernel, nq * slabs, 256, 0, c->stream, rp);
 		HIPCHK(c, hipGetLastError());
-		if (span_end(c, &ts_dense)) return 1;
+		if (!d_pick && span_end(c, &ts_dense)) return 1;
 	}
 	HIPCHK(c, hipGetLastError());
 	c->last_post_cells = 0; // several matrices: not what mpcgpu_get_last_post hands out
@@ -856,7 +883,8 @@ int mpcgpu_align_pairs(mpcgpu_ctx *c, uint32_t npairs, const uint32_t *seq1, con
 		chunk = std::min(chunk, nq); // a halved chunk stays halved
 		std::vector<u64> off(nq + 1, 0);
 		for (u32 q = 0; q < nq; ++q) off[q + 1] = off[q] + (u64)c->len[sx[q]] * c->len[sy[q]];
-		if (dense_posts(c, nq, off)) return 1;
+		if (dense_posts(c, "mpcgpu_align_pairs: pair list with a sequence of more than ~12 000 residues (or MPCGPU_POST=sort): the row-list finishing kernel "
+			"whose candidate lists this entry point rebuilds the dense posteriors from does not take them", nq, off, nullptr)) return 1;
 		if (align_dense(c, nq, sx, sy, off, path_stride, paths + (u64)q0 * path_stride, pathlens + q0, scores ? scores + q0 : nullptr, ea ? ea + q0 : nullptr)) return 1;
 		q0 += nq;
 	}

@@ -51,19 +51,9 @@ int search_chunk_fused(mpcgpu_ctx *c, u64 q0, u32 np, const u32 *px, const u32 *
 {
 	mpcgpu_ctx::SearchState &S = c->se;
 	const StageAGeom g = stage_a_geom(c, np, px, py);
-	if (g.LXlong) return 2; // row-block pairs
 	u32 Lsum_max = 0;
-	for (u32 q = 0; q < np; ++q) {
-		const u32 LX = c->len[px[q]], LY = c->len[py[q]];
-		if (!aln_wave_fits(LX, LY)) return 2; // not a one-wave alignment
-		Lsum_max = std::max(Lsum_max, LX + LY);
-	}
-	if (!post_rows_fits(g.LXmax, g.LYmax, 1024)) return 2;
-	c->have_shard = c->have_store = false;
-	c->shard_is_list = true;
-	c->list_x.assign(px, px + np); c->list_y.assign(py, py + np);
-	c->list_q0 = 0; c->ap_x.clear(); c->ap_y.clear();
-	c->sh_k0 = 0; c->sh_k1 = np;
+	if (!short_list_fits(c, g, np, px, py, &Lsum_max)) return 2;
+	short_list_mark(c, np, px, py);
 	c->sh_nnz.clear(); c->sh_ea.clear();
 	// ---- the slots: the runs of one group; a slot of a group that has its hit keeps count 0 and gets no matrix
 	std::vector<u32> sg, sfirst, slen;
@@ -93,11 +83,8 @@ int search_chunk_fused(mpcgpu_ctx *c, u64 q0, u32 np, const u32 *px, const u32 *
 	memcpy(h + o_by, py, 4 * (size_t)np);
 	memcpy(h + o_off, off.data(), 8 * ((size_t)ns + 1));
 	for (u32 s = 0; s < ns; ++s) { hfirst[s] = sfirst[s]; hcnt[s] = open[sg[s]] ? slen[s] : 0u; }
-	u32 hcount[MPC_HMAX + 1] = {0};
-	std::vector<u32> keys(np);
-	for (u32 q = 0; q < np; ++q) { const u32 H = (c->len[px[q]] + 63) / 64; hcount[H]++; keys[q] = (H << 16) | q; }
-	std::sort(keys.begin(), keys.end());
-	for (u32 q = 0; q < np; ++q) order[q] = keys[q] & 0xffffu;
+	u32 hcount[MPC_HMAX + 1];
+	short_list_order(c, np, px, order, hcount);
 	u32 *pick = (u32 *)(h + o_pick), *acc = (u32 *)(h + o_acc);
 	for (u32 s = 0; s < ns; ++s) pick[s] = acc[s] = MPC_PICK_NONE;
 	// ---- scratch
@@ -113,12 +100,9 @@ int search_chunk_fused(mpcgpu_ctx *c, u64 q0, u32 np, const u32 *px, const u32 *
 	HIPCHK(c, hipMemsetAsync(S.d_flags.p, 0, 4 * (size_t)np, c->stream));
 	const char *d = S.d_in.as<char>();
 	const u32 *bx = (const u32 *)(d + o_bx), *by = (const u32 *)(d + o_by);
-	// ---- forward / backward, one launch per rows-per-lane bin; probabilities, EA, sparsify: a workgroup per pair (align_pairs_small)
-	FbParams fp;
-	fill_fb_params(c, fp, bx, by, g.capc, g.mega);
-	if (launch_fb_bins(c, g, fp, (const u32 *)(d + o_order), hcount, 0)) return 1;
+	// ---- sweeps and finishing kernel (align_pairs_small): sizes, EAs and flags stay on the device
 	const PostIO io = {bx, by, c->d_seq_len.as<u32>(), c->d_cand.as<u64>(), c->d_cand_cnt.as<u32>(), c->d_res.as<u32>(), S.d_nnz.as<u32>(), S.d_ea.as<float>(), S.d_flags.as<u32>(), np};
-	if (launch_post_rows(c, g, io, 1024, 64, np, c->d_sort_scratch, true)) return 1;
+	if (short_list_sweeps(c, g, io, (const u32 *)(d + o_order), hcount)) return 1;
 	// ---- the pick, and the dense posterior and alignment of the picked pairs alone
 	HIPCHK(c, hipEventRecord(S.ev0, c->stream));
 	SearchPickParams sp;
@@ -139,10 +123,7 @@ int search_chunk_fused(mpcgpu_ctx *c, u64 q0, u32 np, const u32 *px, const u32 *
 	ap.post = c->d_aln_post.as<float>(); ap.out_off = (const u64 *)(d + o_off);
 	ap.rev = c->d_aln_rev.as<char>(); ap.rev_stride = Lsum_max; ap.rec = h + o_res; ap.rec_stride = rstride;
 	const size_t smem = aln_wave_smem((u64)g.LXmax + 1);
-	if (smem > S.aln_smem) {
-		(void)hipFuncSetAttribute((const void *)calc_aln_wave_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-		S.aln_smem = smem;
-	}
+	aln_smem_raise(c, 5, (const void *)calc_aln_wave_pick_kernel, smem);
 	TimedSpan ts;
 	if (span_begin(c, 8, &ts)) return 1;
 	MPC_LAUNCH(calc_aln_wave_pick_kernel, ns, 64, smem, c->stream, ap);
@@ -162,35 +143,6 @@ int search_chunk_fused(mpcgpu_ctx *c, u64 q0, u32 np, const u32 *px, const u32 *
 		if (!open[sg[s]] || q < sfirst[s] || q >= sfirst[s] + slen[s] || acc[s] != q - sfirst[s]) return fail(c, "mpcgpu_search_pairs: pick of slot %u out of range (internal error)", s);
 		if (search_accept(c, o, sg[s], q0 + q, h + o_res + (u64)s * rstride, c->len[px[q]], c->len[py[q]], open)) return 1;
 	}
-	return 0;
-}
-
-// The dense posteriors of the nk picked pairs (positions pk[] of the stage-A batch just run) at off[] of d_aln_post, from the candidate
-// lists the batch left: dense_posts' two cases through the indirect kernels
-int search_dense_picked(mpcgpu_ctx *c, const std::vector<u32> &pk, const std::vector<u64> &off)
-{
-	mpcgpu_ctx::SearchState &S = c->se;
-	const u32 nk = (u32)pk.size();
-	const char *post_mode = getenv("MPCGPU_POST");
-	if (!c->sa_post_rows && post_mode && !strcmp(post_mode, "sort"))
-		return fail(c, "mpcgpu_search_pairs: MPCGPU_POST=sort: the row-list finishing kernel whose candidate lists this entry point rebuilds the dense posteriors from is switched off");
-	HIPCHK(c, c->d_aln_post.ensure_grow(off[nk] * 4));
-	if (upload(c, S.d_pick, pk) || upload(c, S.d_off, off)) return 1;
-	DensePostPickParams dp;
-	dp.d.pair_x = c->d_bx.as<u32>(); dp.d.pair_y = c->d_by.as<u32>(); dp.d.seq_len = c->d_seq_len.as<u32>();
-	dp.d.cand = c->d_cand.as<u64>(); dp.d.capc = c->sa_capc; dp.d.cand_cnt = c->d_cand_cnt.as<u32>(); dp.d.long_min = c->sa_long_min;
-	dp.d.out_off = S.d_off.as<u64>(); dp.d.out = c->d_aln_post.as<float>();
-	dp.pick = S.d_pick.as<u32>();
-	if (c->sa_post_rows) MPC_LAUNCH(dense_post_pick_kernel, nk, 256, 0, c->stream, dp);
-	else {
-		DensePostRawPickParams rp;
-		rp.r.d = dp.d; rp.r.use_fma = c->use_fma; rp.pick = dp.pick;
-		rp.r.slabs = (u32)std::max<u64>(1, std::min<u64>(((u64)c->sa_capc + 255) / 256, ((u64)c->prop.multiProcessorCount * 8 + nk - 1) / nk));
-		HIPCHK(c, hipMemsetAsync(c->d_aln_post.p, 0, off[nk] * 4, c->stream));
-		MPC_LAUNCH(dense_post_raw_pick_kernel, nk * rp.r.slabs, 256, 0, c->stream, rp);
-	}
-	HIPCHK(c, hipGetLastError());
-	c->last_post_cells = 0;
 	return 0;
 }
 
@@ -237,7 +189,9 @@ int search_chunk_general(mpcgpu_ctx *c, u64 q0, u32 np, const u32 *px, const u32
 			std::vector<float> tsc(nk, 0.0f);
 			if (search_events(c)) return 1;
 			HIPCHK(c, hipEventRecord(S.ev0, c->stream));
-			if (search_dense_picked(c, rpk, roff)) return 1;
+			// the dense posteriors of the picked pairs alone (positions rpk[] of the batch) at roff[] of d_aln_post
+			if (upload(c, S.d_pick, rpk) || dense_posts(c, "mpcgpu_search_pairs: MPCGPU_POST=sort: the row-list finishing kernel whose candidate lists this entry point rebuilds the "
+				"dense posteriors from is switched off", nk, roff, S.d_pick.as<u32>())) return 1;
 			if (align_dense(c, nk, kx.data() + k0, ky.data() + k0, roff, stride, tpaths.data(), tlens.data(), tsc.data(), nullptr)) return 1;
 			HIPCHK(c, hipEventRecord(S.ev1, c->stream));
 			if (search_elapsed(c)) return 1;

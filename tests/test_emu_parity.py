@@ -88,13 +88,16 @@ def test_emu_relax_two_slots_per_pair(emu):
     P.assert_same((stages, ea), P.run_oracle(seqs), "nent=2")
 
 
-@pytest.mark.parametrize("kernel", ["by size", "one wave", "waves", "lds rows"])
+@pytest.mark.parametrize("kernel", ["by size", "one wave", "waves", "lds rows", "column tiles"])
 def test_emu_calc_aln(emu, kernel, monkeypatch):
     """CalcAlnFlat + TraceBackFlat on the device (kernels_aln.h) vs the oracle: same path string,
     same score bits, including tie cases (equal B/X/Y candidates) and general non-posterior input."""
     # calc_aln_wave_kernel (<= 512 columns) / calc_aln_quad_kernel (<= 4096 columns) / calc_aln_kernel; a kernel that cannot take
-    # a matrix leaves it to the next one
-    monkeypatch.setenv("MPCGPU_ALN_KERNEL", str(["by size", "one wave", "waves", "lds rows"].index(kernel)))
+    # a matrix leaves it to the next one; calc_aln_tiled_kernel takes every matrix, here in tiles of 550 columns: the 1101 columns
+    # (with column 0) of the widest matrix are two whole tiles and a tile of exactly one column
+    monkeypatch.setenv("MPCGPU_ALN_KERNEL", str(["by size", "one wave", "waves", "lds rows", "column tiles"].index(kernel)))
+    if kernel == "column tiles":
+        monkeypatch.setenv("MPCGPU_ALN_TILE", "550")
     import _oracle as O
     from muscle_amd._lib import MpcGpu
     rng = np.random.default_rng(5)

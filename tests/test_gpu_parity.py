@@ -396,14 +396,17 @@ def test_relax_window_rows_wider_than_the_span_field(monkeypatch):
         P.assert_same(got, want, "window escape %s" % extra)
 
 
-@pytest.mark.parametrize("kernel", ["by size", "one wave", "waves", "lds rows"])
+@pytest.mark.parametrize("kernel", ["by size", "one wave", "waves", "lds rows", "column tiles"])
 def test_calc_aln_paths(kernel, monkeypatch):
     """CalcAlnFlat + TraceBackFlat on the device: integer traceback bit-for-bit (path string) and
     score bits, vs the golden paths of the compiled reference (pairs_small) and vs the oracle on
     dense MSA-sized matrices with many exact ties."""
     # calc_aln_wave_kernel (<= 512 columns) / calc_aln_quad_kernel (<= 4096 columns) / calc_aln_kernel; a kernel that cannot take
-    # a matrix leaves it to the next one
-    monkeypatch.setenv("MPCGPU_ALN_KERNEL", str(["by size", "one wave", "waves", "lds rows"].index(kernel)))
+    # a matrix leaves it to the next one; calc_aln_tiled_kernel takes every matrix, here in tiles of 1500 columns: the 4501 columns
+    # (with column 0) of the 40 x 4500 matrix end in a tile of exactly one column, 2500 / 4000 take two / three tiles, the narrow ones one
+    monkeypatch.setenv("MPCGPU_ALN_KERNEL", str(["by size", "one wave", "waves", "lds rows", "column tiles"].index(kernel)))
+    if kernel == "column tiles":
+        monkeypatch.setenv("MPCGPU_ALN_TILE", "1500")
     import _oracle as O
     g = MpcGpu(0)
     z = G.load("pairs_small")
